@@ -4,12 +4,13 @@ synthetic 10 000 loci x 1 000 sites, 4 taxa, JC69, 1 rate category, at N GPUs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] ...
 
-A "step" is `iterations_per_step` MCMC ITERATIONS of the device-resident A00 sampler over all loci (config c2) — an
-iteration: per locus tips-1 gene-node age proposals and 2 tips-2 prune/regraft proposals, a theta step per population, a
-rubber-band tau step per divergence and one mixing step, every proposal, density, likelihood and accept/reject on the
-GPU (bpa_sampler_t; same posterior as the unmodified program, tests/test_a00_posterior.py).  The count is chosen so that
-the timed region lasts >= 0.25 s whatever --steps is (an iteration takes ~0.1 ms).  On one GPU all iterations of a step
-are ONE persistent launch (csrc/sweep2.hpp).  `value` is iterations/s; `roofline` is that kernel's; `cpu_baseline` is the
+A "step" is one MCMC ITERATION of the device-resident A00 sampler over all loci (config c2) — per locus tips-1 gene-node
+age proposals and 2 tips-2 prune/regraft proposals, a theta step per population, a rubber-band tau step per divergence
+and one mixing step, every proposal, density, likelihood and accept/reject on the GPU (bpa_sampler_t; same posterior as
+the unmodified program, tests/test_a00_posterior.py).  --steps K times exactly K of them and `ms_per_step` is the time of
+one (an iteration of c2 takes ~0.1 ms: choose K for the length of the timed region).  On one GPU up to 4 096 iterations
+are ONE persistent launch (csrc/sweep2.hpp).  --dump-outputs DIR writes the sampler's state after the last timed step
+(dump_sampler_outputs); with the same arguments the inputs and the number of iterations run are the same on every run.  `value` is iterations/s; `roofline` is that kernel's; `cpu_baseline` is the
 unmodified reference program's whole MCMC iterations/s at its best thread count on this box (like for like with `value`).
 Next to it, as before:
 
@@ -35,7 +36,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")     # as bpp_amd/__init__.py does (here too: torch may bring the HIP runtime in first when N > 1)
 
 import numpy as np  # noqa: E402
 
@@ -992,8 +992,9 @@ class Dist:
         log("sums between ranks: " + ("one-shot p2p all-reduce (self-test against RCCL passed)" if p2p else "RCCL all-reduce"))
 
 
-def run_tape(eng, cfg, config_key, data, loci, args, D, steps, warmup):
-    """the likelihood hot path alone on a resident proposal tape; returns the section's dict"""
+def run_tape(eng, cfg, config_key, data, loci, args, D, steps, warmup, dump_dir=None):
+    """the likelihood hot path alone on a resident proposal tape; returns the section's dict.  dump_dir: the per-locus lnL
+    every plan of the last timed iteration computed, concatenated in launch order, is written there (--dump-outputs)"""
     import bpp_amd
     from bpp_amd.schedule import A00Schedule, TreeState
     nloci = len(data)
@@ -1137,6 +1138,11 @@ def run_tape(eng, cfg, config_key, data, loci, args, D, steps, warmup):
         D.dist.all_reduce(want)
         allreduce_check = "ok" if abs(got - float(want.item())) <= 1e-9 * abs(got) else f"MISMATCH {got} vs {float(want.item())}"
 
+    dumped = None
+    if dump_dir and rank == 0:
+        last = plans[(warmup + steps - 1) % len(plans)]
+        dumped = save_outputs(dump_dir, dict(plan_lnl=np.concatenate([np.asarray(p.lnl(), dtype=np.float64) for p in last]),
+                                             plan_loci=np.array([len(st.loci) for st in iters[(warmup + steps - 1) % len(iters)]], dtype=np.float64)))
     ms_per_step = 1e3 * elapsed / steps
     total_loci = D.sum_int(nloci) if D else nloci
     roofline = None
@@ -1165,7 +1171,7 @@ def run_tape(eng, cfg, config_key, data, loci, args, D, steps, warmup):
         site_lnl_updates_per_s=round(it_pattern_updates * (total_loci / nloci) * steps / elapsed),
         node_updates_per_iteration=round(float(it_node_updates)),
         gflops_partials=round(it_flops * (total_loci / nloci) * steps / elapsed / 1e9, 2),
-        roofline=add_frac_pmc(roofline), allreduce_check=allreduce_check, codes_ratio=round(codes_ratio_k1k2, 5),
+        roofline=add_frac_pmc(roofline), allreduce_check=allreduce_check, codes_ratio=round(codes_ratio_k1k2, 5), dumped_outputs=dumped,
         note="pre-recorded proposal tape, accept/reject by a seeded coin: the likelihood path alone (no MCMC decision)")
     for it in plans:
         for p in it:
@@ -1179,12 +1185,14 @@ def run_tape(eng, cfg, config_key, data, loci, args, D, steps, warmup):
 PROGRAM_FT = dict(gage=18.5, gspr=0.0019, theta=3e-5, tau=1.9e-5, mix=0.0059)
 
 
-def run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup, moves="program", codes_ratio=None):
+def run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup, moves="program", codes_ratio=None, headline=False):
     """BASELINE's metric proper: whole A00 MCMC iterations/s with every decision on the device.
     moves = "program" (JC69 loci on the persistent kernel): BPP's own iteration — its generator and Bactrian-Laplace windows
     (bpa_sampler_set_proposal_kernel), theta by the metropolized Gibbs draw 9 times in 10, thetas re-drawn inside the
     rubber-band and the mixing step (bpa_sampler_set_program_moves: stree.c:3957, 5840; prop_mixing.c:272);
-    "uniform": our 64-bit streams, uniform windows, a sliding-window theta, no re-draws (rounds 1-3's headline)."""
+    "uniform": our 64-bit streams, uniform windows, a sliding-window theta, no re-draws (rounds 1-3's headline).
+    headline: a step is one iteration, so that --steps is the number of timed iterations and nothing the run computes
+    depends on a timing; --dump-outputs then writes the state the timed iterations left."""
     import bpp_amd
     from bpp_amd import synth
     nloci = len(data)
@@ -1275,19 +1283,21 @@ def run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup, moves
         # the program's burn-in (finetune = 1): 800 iterations, the step lengths reset from the acceptance proportions after every
         # quarter and at the end (bpa_sampler_burnin: reset_finetune, method.c:1508-1516, 5364) — outside the timed region
         burnin_ft = smp.burnin(800)
-    # A step = `ips` MCMC iterations, chosen so that the timed region lasts >= 0.25 s whatever --steps is (an iteration
-    # of config 2 takes ~0.1 ms: 20 of them would be a 2 ms region); the rate does not depend on it.  Every rank takes
-    # the same count (the ranks enter the same collectives).
+    # A step of the headline = one MCMC iteration.  A step of the other sections = `ips` iterations, chosen so that their
+    # timed region lasts >= 0.25 s (an iteration of config 2 takes ~0.1 ms: 20 of them would be a 2 ms region); the rate
+    # does not depend on it.  Every rank takes the same count (the ranks enter the same collectives).
     smp.iterate(max(warmup, 1))
     sync()
-    probe = 2 if generic else 20
-    t0 = time.perf_counter()
-    smp.iterate(probe)
-    sync()
-    est = (time.perf_counter() - t0) / probe
-    if D is not None:
-        est = D.max(est)
-    ips = max(1, int(np.ceil(0.3 / max(est * steps, 1e-9))))      # (0.3: the probe runs a little slower than the long launch)
+    ips = 1
+    if not headline:
+        probe = 2 if generic else 20
+        t0 = time.perf_counter()
+        smp.iterate(probe)
+        sync()
+        est = (time.perf_counter() - t0) / probe
+        if D is not None:
+            est = D.max(est)
+        ips = max(1, int(np.ceil(0.3 / max(est * steps, 1e-9))))      # (0.3: the probe runs a little slower than the long launch)
     niter = steps * ips
     while True:
         smp.iterate(warmup)
@@ -1314,7 +1324,7 @@ def run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup, moves
                         smp.close()
                     except Exception:       # noqa: BLE001
                         pass
-                    return run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup)
+                    return run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup, headline=headline)
                 continue
         tm = smp.timing()
         smp.enable_timing(0)
@@ -1439,8 +1449,44 @@ def run_sampler(eng, cfg, data, loci, args, D, first_locus, steps, warmup, moves
                     "the reference (tests/test_gpu_sampler.py, tests/test_gpu_host_driver.py)")
     if D is not None and D.p2p is not None and D.p2p.status() != 0:
         out = dict(error="a p2p exchange timed out during the sampler section: its numbers are void (rerun without --p2p-sums)")
+    elif headline and args.dump_outputs and (D is None or D.rank == 0):
+        out["dumped_outputs"] = dump_sampler_outputs(smp, nloci, args.dump_outputs)
     smp.close()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def save_outputs(out_dir, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES and all(a.dtype in (np.float32, np.float64) for a in arrays.values()), total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return dict(dir=out_dir, files=sorted(arrays), bytes=total)
+
+
+def dump_sampler_outputs(smp, nloci, out_dir):
+    """--dump-outputs: what a caller of the sampler receives after the last timed iteration, as float64 .npy files —
+    the species tree's taus and thetas, the chain's total lnL and every locus's gene tree (node ages, children, parents,
+    root, lnL, MSC log density).  Loci beyond what fits in DUMP_LIMIT_BYTES: a seeded sample of them, the same on every run."""
+    width = 2 * max(smp.ntips) - 1
+    max_loci = (DUMP_LIMIT_BYTES - (1 << 20)) // ((4 * width + 5) * 8)
+    ks = np.arange(nloci) if nloci <= max_loci else np.sort(np.random.default_rng(0).choice(nloci, max_loci, replace=False))
+    trees = [smp.tree(int(k)) for k in ks]
+
+    def nodes(key):
+        a = np.full((len(trees), width), np.nan)
+        for i, t in enumerate(trees):
+            a[i, :len(t[key])] = t[key]
+        return a
+    arrays = dict(taus=np.array(smp.taus(), dtype=np.float64), thetas=np.array(smp.thetas(), dtype=np.float64),
+                  total_lnl=np.array([smp.summary()["total_lnl"]]), locus_index=ks.astype(np.float64),
+                  locus_lnl=np.array([t["lnl"] for t in trees]), locus_logpr=np.array([t["logpr"] for t in trees]),
+                  locus_root=np.array([t["root"] for t in trees], dtype=np.float64),
+                  node_time=nodes("time"), node_left=nodes("left"), node_right=nodes("right"), node_parent=nodes("parent"))
+    return dict(save_outputs(out_dir, arrays), loci=len(ks))
 
 
 def main():
@@ -1448,6 +1494,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step computed as DIR/<name>.npy (float64, <= 64 MB in all)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--loci", type=int, default=None, help="loci of the data set (default: the config's)")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
@@ -1544,10 +1592,13 @@ def main():
     tape_steps = None
     if not (args.config in ("c2", "c3") and args.no_tape):
         log("section: likelihood-only tape")
-        tape_sec, tape_steps = run_tape(eng, cfg, args.config, data, loci, args, D, args.steps, args.warmup)
+        tape_headline = args.no_sampler or args.config not in ("c2", "c3", "c4")
+        tape_sec, tape_steps = run_tape(eng, cfg, args.config, data, loci, args, D, args.steps, args.warmup,
+                                        dump_dir=args.dump_outputs if tape_headline else None)
     if args.config in ("c2", "c3", "c4") and not args.no_sampler:
         log("section: device-resident sampler (headline)")
-        sampler_sec = run_sampler(eng, cfg, data, loci, args, D, first_locus, args.steps, args.warmup, codes_ratio=(tape_sec or {}).get("codes_ratio"))
+        sampler_sec = run_sampler(eng, cfg, data, loci, args, D, first_locus, args.steps, args.warmup, codes_ratio=(tape_sec or {}).get("codes_ratio"),
+                                  headline=True)
         if "error" in sampler_sec:
             log(sampler_sec["error"])
         elif args.config == "c2" and D is None and not args.no_uniform_kernel:

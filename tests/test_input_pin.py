@@ -107,10 +107,9 @@ def test_frogs_lnl_reference_vs_oracle_on_loader_output(G):
         rl.free()
 
 
-ANOPH = "/root/reference/examples/anopheles"
+ANOPH = os.path.join(HERE, "golden", "anopheles")      # the reference's examples/anopheles data files, verbatim
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ANOPH, "loci_realign.txt")), reason="reference examples not present")
 def test_anopheles_config5_pipeline_matches_reference(G):
     """BASELINE config 5 (examples/anopheles: 100 loci x 12 sequences, cleandata = 1, JC69): reader -> missing
     sequences -> ambiguous sites cut in the reference's swap order -> compression; labels, kept sites, pattern

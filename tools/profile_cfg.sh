@@ -15,6 +15,8 @@ STEPS=${STEPS:-6}
 # JSON then says which (a box's budget can end a call: better a profile without the last SQ sets than none)
 export BPP_AMD_SYNTH_CACHE=/tmp/synth_cache_prof; mkdir -p $BPP_AMD_SYNTH_CACHE
 T0=$(date +%s); DEADLINE=${PROFILE_DEADLINE_S:-100000}
+# every GPU step runs under its own time limit (STEP_S) and a failed step ends the script: nothing more is started on the card
+STEP_S=${STEP_S:-900}
 python3 - <<PY
 import sys; sys.path.insert(0, "$R")
 import importlib.util
@@ -27,14 +29,14 @@ SKIPPED=""
 pass() {   # pass <name> <rocprofv3 arguments...>
   local name=$1; shift
   if [ $(( $(date +%s) - T0 )) -gt $DEADLINE ]; then SKIPPED="$SKIPPED $name"; return; fi
-  rocprofv3 "$@" -f csv -d $W/$name -o p -- $BENCH > /dev/null 2> $W/$name.log
+  timeout -k 10 $STEP_S rocprofv3 "$@" -f csv -d $W/$name -o p -- $BENCH > /dev/null 2> $W/$name.log || { echo "[profile_cfg] $CFG $name failed: $?"; exit 1; }
   echo "[profile_cfg] $CFG $name done at +$(( $(date +%s) - T0 ))s"
 }
 BENCH="python $R/bench.py --full-record $W/full.json --config $CFG --steps $STEPS --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
 echo "[profile_cfg] $CFG data set ready at +$(( $(date +%s) - T0 ))s"
-$BENCH --full-record $W/full_plain.json > $W/bench_plain.json 2> $W/plain.log
+timeout -k 10 $STEP_S $BENCH --full-record $W/full_plain.json > $W/bench_plain.json 2> $W/plain.log || { echo "[profile_cfg] $CFG plain run failed: $?"; exit 1; }
 echo "[profile_cfg] $CFG plain run done at +$(( $(date +%s) - T0 ))s"
-rocprofv3 --kernel-trace --stats -f csv -d $W/trace -o p -- $BENCH > $W/bench_trace.json 2> $W/trace.log
+timeout -k 10 $STEP_S rocprofv3 --kernel-trace --stats -f csv -d $W/trace -o p -- $BENCH > $W/bench_trace.json 2> $W/trace.log || { echo "[profile_cfg] $CFG trace pass failed: $?"; exit 1; }
 echo "[profile_cfg] $CFG trace pass done at +$(( $(date +%s) - T0 ))s"
 pass pmc_fetch --pmc FETCH_SIZE
 pass pmc_write --pmc WRITE_SIZE
