@@ -2,7 +2,7 @@
 """bench.py — BASELINE.json's metric on the configuration it is quoted on (configs[1]): MCMC iterations/s of A00 on
 synthetic 10 000 loci x 1 000 sites, 4 taxa, JC69, 1 rate category, at N GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--scaling weak|strong] [--full] ...
 
 A "step" is one MCMC ITERATION of the device-resident A00 sampler over all loci (config c2) — per locus tips-1 gene-node
 age proposals and 2 tips-2 prune/regraft proposals, a theta step per population, a rubber-band tau step per divergence
@@ -10,17 +10,22 @@ and one mixing step, every proposal, density, likelihood and accept/reject on th
 the unmodified program, tests/test_a00_posterior.py).  --steps K times exactly K of them and `ms_per_step` is the time of
 one (an iteration of c2 takes ~0.1 ms: choose K for the length of the timed region).  On one GPU up to 4 096 iterations
 are ONE persistent launch (csrc/sweep2.hpp).  --dump-outputs DIR writes the sampler's state after the last timed step
-(dump_sampler_outputs); with the same arguments the inputs and the number of iterations run are the same on every run.  `value` is iterations/s; `roofline` is that kernel's; `cpu_baseline` is the
-unmodified reference program's whole MCMC iterations/s at its best thread count on this box (like for like with `value`).
-Next to it, as before:
+(dump_sampler_outputs); with the same arguments the inputs and the number of iterations run are the same on every run.  `value` is iterations/s; `roofline` is that kernel's.
+
+A plain run does only that: it makes the data set, runs the sampler's burn-in, warms up, times the K steps, writes
+--dump-outputs and prints the line.  --full adds every other section, each a run of its own:
 
   likelihood_only   the hot path alone on a pre-recorded proposal tape (bpp_amd/schedule.py; accept/reject by a seeded
                     coin): resident batched plans, the per-locus steps of an iteration as one chain launch, the all-loci
-                    steps one launch each.  This is also what `--config c3|c4` time (`value` then: tape iterations/s of
-                    that config's own loci), and what `other_configs` carries for c3 / c4 in the default run.
+                    steps one launch each.  This is also what `--no-sampler` times (`value` then: tape iterations/s, in
+                    a plain run too), and what `other_configs` carries for c3 / c4.
   cpu_tape_replay   the same tape through the REAL reference's locus API (oracle/_ref, AVX2), one core and all cores
                     (comparable with likelihood_only; `speedups` holds both ratios).
-  reference_program_on_host   the unmodified program's whole MCMC iterations/s by thread count (`cpu_baseline` = its best).
+  reference_program_on_host   the unmodified program's whole MCMC iterations/s by thread count; `cpu_baseline` = its best,
+                    like for like with `value`.
+  other_configs     configs 1, 3, 4 and 5 and the mixed set on the same GPU (--config c2 on one GPU).
+  host_control_in_c, scale_projection, device_uniform_kernel (the sampler with uniform-window moves) on one GPU; at N > 1
+                    the other scaling mode (`value_weak` / `value_strong`) and the tape's all-reduce self-check.
 
 N > 1 (torch.distributed, one rank per GPU): loci sharded, no data-path collective; the only exchange is the sum an
 all-loci step is decided on.  --scaling weak (default; every rank owns the config's loci, `value` in 10k-locus
@@ -1503,14 +1508,17 @@ def main():
                          "config's size, loci dealt to the ranks by the reference's zig-zag (threads.c:265-353)")
     ap.add_argument("--full-record", default=None,
                     help="where the full record goes (default: bench_full.json next to this file and under gpurun_out/); the stdout line is the compact one")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every section the headline does not need (see the module's docstring); the --no-* switches "
+                         "below leave parts of it out.  Without it the run times the headline alone")
     ap.add_argument("--tape-iters", type=int, default=4, help="distinct A00 iterations in the resident tape")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sampler", action="store_true", help="c2: skip the device-resident sampler (`value` is then the tape's)")
     ap.add_argument("--no-tape", action="store_true", help="c2: skip the likelihood-only tape section")
     ap.add_argument("--no-host-control", action="store_true", help="c2: skip the host-driven section (a00_driver.c on the GPU back-end)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the c3 / c4 tape sections of the default run")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the other configurations (c1, c3, c4, c5, the mixed set)")
     ap.add_argument("--efficiency", action="store_true",
-                    help="run the ESS/s section (the program's chain with its burn-in next to the device's: ~50 s more) and the long thread sweep")
+                    help="with --full: run the ESS/s section (the program's chain with its burn-in next to the device's: ~50 s more) and the long thread sweep")
     ap.add_argument("--no-efficiency", action="store_true",
                     help="skip the ESS/s section (one more 1 900-iteration run of the reference program with its burn-in, BPP's move kernel on the device)")
     ap.add_argument("--no-bpp-program", action="store_true",
@@ -1541,6 +1549,8 @@ def main():
     ap.add_argument("--host-in-loop", action="store_true",
                     help="tape: copy the per-locus lnL of every step back to the host before launching the next")
     args = ap.parse_args()
+    if args.efficiency and not args.full:
+        ap.error("--efficiency is a section of the full run: add --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1590,9 +1600,10 @@ def main():
 
     tape_sec = sampler_sec = None
     tape_steps = None
-    if not (args.config in ("c2", "c3") and args.no_tape):
+    # the tape is the headline with --no-sampler; next to the sampler it is a section of the full run
+    tape_headline = args.no_sampler or args.config not in ("c2", "c3", "c4")
+    if (tape_headline or args.full) and not (args.config in ("c2", "c3") and args.no_tape):
         log("section: likelihood-only tape")
-        tape_headline = args.no_sampler or args.config not in ("c2", "c3", "c4")
         tape_sec, tape_steps = run_tape(eng, cfg, args.config, data, loci, args, D, args.steps, args.warmup,
                                         dump_dir=args.dump_outputs if tape_headline else None)
     if args.config in ("c2", "c3", "c4") and not args.no_sampler:
@@ -1601,13 +1612,13 @@ def main():
                                   headline=True)
         if "error" in sampler_sec:
             log(sampler_sec["error"])
-        elif args.config == "c2" and D is None and not args.no_uniform_kernel:
+        elif args.full and args.config == "c2" and D is None and not args.no_uniform_kernel:
             # rounds 1-3's headline iteration (half the program's effective samples per iteration), for comparison
             u = run_sampler(eng, cfg, data, make_loci(eng, data), args, None, first_locus, max(args.steps // 4, 5), args.warmup, moves="uniform", codes_ratio=(tape_sec or {}).get("codes_ratio"))
             sampler_sec["device_uniform_kernel"] = {k: u[k] for k in ("iterations_per_s", "ms_per_iteration", "acceptance", "moves", "roofline") if k in u}
 
     other_mode = None
-    if D is not None and world > 1 and sampler_sec is not None and "error" not in sampler_sec and not scaling_given:
+    if args.full and D is not None and world > 1 and sampler_sec is not None and "error" not in sampler_sec and not scaling_given:
         om = "strong" if args.scaling == "weak" else "weak"
         try:
             d_o, fl_o = make_data(om)
@@ -1622,7 +1633,7 @@ def main():
             other_mode = dict(scaling=om, error=str(ex)[:300])
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and tape_steps is not None:
+    if args.full and rank == 0 and not args.no_cpu_baseline and tape_steps is not None:
         init, iters = tape_steps
         n_cpu_iter = min(2, len(iters))
         log("section: CPU tape replay")
@@ -1643,10 +1654,10 @@ def main():
     bpp_prog = None
     chain = None
     # the ESS/s section (a 2 900-iteration run of the program with its burn-in + the device's chain: ~50 s) is opt-in since round 6
-    # (--efficiency): the default run must finish in about two minutes; the line carries the committed long runs' ESS-per-iteration
+    # (--efficiency): the full run must finish in about two minutes; the line carries the committed long runs' ESS-per-iteration
     # ratios (profiles/r*/ess_*.json) either way
     want_eff = args.efficiency and not args.no_efficiency
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_cpu_baseline and not args.no_bpp_program:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.no_cpu_baseline and not args.no_bpp_program:
         try:
             ncores = os.cpu_count() or 1
             # one thread, what the CPU quota grants (the box shows 256 logical cores and grants 16: more threads than that are
@@ -1680,7 +1691,7 @@ def main():
 
     # ---- the other single-GPU configurations of BASELINE.json on the same box (tape = likelihood path)
     others = None
-    if args.config == "c2" and world == 1 and D is None and not args.no_other_configs:
+    if args.full and args.config == "c2" and world == 1 and D is None and not args.no_other_configs:
         others = {}
         for key, k_steps, k_warm in (("c3", 12, 2), ("c4", 6, 1)):
             try:
@@ -1747,7 +1758,7 @@ def main():
     # ---- MCMC control on the host in C (last: libgomp pins the calling thread under OMP_PROC_BIND, and threads or
     # processes started afterwards would inherit that one-CPU mask — the CPU baselines above must not)
     host_sec = None
-    if rank == 0 and world == 1 and D is None and args.config == "c2" and not args.no_host_control:
+    if args.full and rank == 0 and world == 1 and D is None and args.config == "c2" and not args.no_host_control:
         mask = os.sched_getaffinity(0) if hasattr(os, "sched_getaffinity") else None
         try:
             q = cpu_quota()
@@ -1760,7 +1771,7 @@ def main():
 
     # ---- what one rank of an N-GPU strong-scaling run of this config would work on, measured here (N = 1 only)
     projection = None
-    if rank == 0 and world == 1 and D is None and args.config in ("c2", "c3", "c4") and not args.no_scale_projection and not args.no_sampler:
+    if args.full and rank == 0 and world == 1 and D is None and args.config in ("c2", "c3", "c4") and not args.no_scale_projection and not args.no_sampler:
         try:
             log("section: scale projection")
             projection = scale_projection(args.config, cfg, data, args)

@@ -5,6 +5,8 @@ import glob
 import importlib.util
 import json
 import os
+import subprocess
+import sys
 
 import pytest
 
@@ -53,6 +55,12 @@ def test_an_oversized_record_still_gives_a_short_line():
 def test_bench_prints_the_compact_line_only():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.count("print(json.dumps(") == 1 and "print(json.dumps(compact_line(out)" in src
+
+
+def test_efficiency_belongs_to_the_full_run():
+    """the ESS/s section is a section of --full: asked for without it, bench.py stops at its arguments, before any GPU work"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--efficiency"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-500:]
 
 
 # ---- round 6 (VERDICT r5, task 5): the line's figures share their denominators

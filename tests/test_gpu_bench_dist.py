@@ -25,7 +25,7 @@ def run_bench(extra, tmp=None, world=2):
         port = s.getsockname()[1]
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", BENCH_FORCE_DEVICE="0")
     cmd = ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2"] +
+            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2", "--full"] +
            ([] if "--loci" in extra else ["--loci", "1500"]) + ["--no-cpu-baseline", "--full-record", full_path] + extra)
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -104,12 +104,12 @@ def test_two_rank_bench_line_carries_both_scalings():
 
 
 def test_one_gpu_bench_line_quick():
-    """the driver's own form (`python bench.py --gpus 1 --steps K --warmup W`) with the side sections switched off: the last
-    stdout line is the compact object with the contract's keys, `roofline` with its three fractions and a warning-free `frac`,
-    the full record goes where --full-record says"""
+    """the full run (`python bench.py --gpus 1 --steps K --warmup W --full`) with the side sections switched off but the
+    likelihood-only tape: the last stdout line is the compact object with the contract's keys, `roofline` with its three
+    fractions and a warning-free `frac`, the full record goes where --full-record says"""
     import tempfile
     full_path = os.path.join(tempfile.mkdtemp(prefix="bench1_"), "full.json")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--loci", "2000", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--loci", "2000", "--full", "--no-cpu-baseline",
            "--no-other-configs", "--no-host-control", "--no-scale-projection", "--no-uniform-kernel", "--full-record", full_path]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -125,3 +125,38 @@ def test_one_gpu_bench_line_quick():
     assert smp["kind"] == "persistent" and smp["moves"].startswith("the program's") and smp["step_lengths_after_burnin"]["gage"] > 0
     lo = d["likelihood_only"]
     assert lo["it_s"] > 0 and lo["frac_codes"] <= lo["frac"]
+
+
+def test_one_gpu_plain_bench_line_is_the_headline_alone():
+    """the driver's own form (`python bench.py --gpus 1 --steps K --warmup W`): the device-resident sampler alone (no tape, no CPU
+    baseline, no other configuration), and the state its timed iterations leave (--dump-outputs) is the one the --full run's
+    headline leaves after the likelihood-only tape ran on the same loci"""
+    import tempfile
+    import numpy as np
+    tmp = tempfile.mkdtemp(prefix="bench_plain_")
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--loci", "2000"]
+    r = subprocess.run(common + ["--full-record", os.path.join(tmp, "plain.json"), "--dump-outputs", os.path.join(tmp, "plain")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    full = json.load(open(os.path.join(tmp, "plain.json")))
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert line["metric"] == full["metric"] == base["metric"] and line["unit"] == "iterations/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["steps"] == 4 and line["warmup"] == 2
+    smp = full["device_resident_sampler"]
+    assert line["value"] == full["value"] == smp["iterations_per_s_10k_loci"] > 0 and line["ms_per_step"] == smp["ms_per_step"] > 0
+    assert smp["kind"] == "persistent" and smp["steps"] == 4 and "device_uniform_kernel" not in smp
+    for k in ("likelihood_only", "cpu_baseline", "cpu_tape_replay", "reference_program_on_host", "statistical_efficiency",
+              "other_configs", "host_control_in_c", "scale_projection"):
+        assert full[k] is None, k
+    assert "section: likelihood-only tape" not in r.stderr
+    # the same headline after the full run's tape section: the same inputs, the same iterations, the same state
+    r2 = subprocess.run(common + ["--full", "--no-cpu-baseline", "--no-other-configs", "--no-host-control", "--no-scale-projection",
+                                  "--no-uniform-kernel", "--full-record", os.path.join(tmp, "full.json"), "--dump-outputs", os.path.join(tmp, "full")],
+                        cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    assert json.load(open(os.path.join(tmp, "full.json")))["likelihood_only"]["steps"] == 4
+    names = sorted(f for f in os.listdir(os.path.join(tmp, "plain")) if f.endswith(".npy"))
+    assert "locus_lnl.npy" in names and names == sorted(f for f in os.listdir(os.path.join(tmp, "full")) if f.endswith(".npy"))
+    for f in names:
+        assert np.array_equal(np.load(os.path.join(tmp, "plain", f)), np.load(os.path.join(tmp, "full", f)), equal_nan=True), f

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 CFGS=${@:-c3 c4}
 (timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_tape.py tests/test_gpu_edges.py tests/test_gpu_gsampler.py tests/test_gpu_fullsize.py -x -q -m gpu > gpurun_out/t2.log 2>&1; tail -3 gpurun_out/t2.log)
-B="--steps 6 --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
+B="--full --steps 6 --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
 for c in $CFGS; do
   python bench.py --config $c $B --full-record gpurun_out/full_${c}_new.json 2> gpurun_out/b_${c}_new.err | tail -1 > gpurun_out/b_${c}_new.json
   BPA_KLANE_V2=1 BPA_S20_KERNEL=pipe python bench.py --config $c $B --full-record gpurun_out/full_${c}_old.json 2> gpurun_out/b_${c}_old.err | tail -1 > gpurun_out/b_${c}_old.json

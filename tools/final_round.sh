@@ -34,8 +34,9 @@ for c in c3 c4; do
   echo "timeline $c rc=$? t=$(( $(date +%s) - $(cat gpurun_out/final_t0) ))"
 done
 cd $R
-timeout 480 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_default.json 2> gpurun_out/bench_default.log
+# the full run (--full): the committed line carries every section (tests/test_bench_line.py reads `likelihood_only` and `configs`);
+# its line, record and log go where the round's profiles are committed
+timeout 480 python bench.py --full --steps 20 --warmup 5 --full-record profiles/$TAG/bench_full.json > profiles/$TAG/bench_default.json 2> profiles/$TAG/bench_default.log
 echo "bench rc=$? t=$(( $(date +%s) - $(cat gpurun_out/final_t0) ))"
-cp -f bench_full.json gpurun_out/bench_full.json 2>/dev/null
-grep "section" gpurun_out/bench_default.log | cut -c1-120
-tail -c 600 gpurun_out/bench_default.json
+grep "section" profiles/$TAG/bench_default.log | cut -c1-120
+tail -c 600 profiles/$TAG/bench_default.json

@@ -32,7 +32,7 @@ pass() {   # pass <name> <rocprofv3 arguments...>
   timeout -k 10 $STEP_S rocprofv3 "$@" -f csv -d $W/$name -o p -- $BENCH > /dev/null 2> $W/$name.log || { echo "[profile_cfg] $CFG $name failed: $?"; exit 1; }
   echo "[profile_cfg] $CFG $name done at +$(( $(date +%s) - T0 ))s"
 }
-BENCH="python $R/bench.py --full-record $W/full.json --config $CFG --steps $STEPS --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
+BENCH="python $R/bench.py --full --full-record $W/full.json --config $CFG --steps $STEPS --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
 echo "[profile_cfg] $CFG data set ready at +$(( $(date +%s) - T0 ))s"
 timeout -k 10 $STEP_S $BENCH --full-record $W/full_plain.json > $W/bench_plain.json 2> $W/plain.log || { echo "[profile_cfg] $CFG plain run failed: $?"; exit 1; }
 echo "[profile_cfg] $CFG plain run done at +$(( $(date +%s) - T0 ))s"

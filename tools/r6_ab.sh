@@ -5,7 +5,7 @@ TAG=$1; CFG=$2; shift 2
 for kv in "$@"; do export "$kv"; done
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
 export BPP_AMD_SYNTH_CACHE=/tmp/synth_cache_prof; mkdir -p $BPP_AMD_SYNTH_CACHE
-B="--steps 6 --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
+B="--full --steps 6 --warmup 2 --no-cpu-baseline --no-other-configs --no-host-control --no-bpp-program --no-efficiency --no-scale-projection"
 timeout 400 python bench.py --config $CFG $B --full-record gpurun_out/ab_${CFG}_$TAG.json 2> gpurun_out/ab_${CFG}_$TAG.err | tail -1 > /dev/null
 python - <<P
 import json
