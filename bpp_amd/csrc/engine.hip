@@ -98,6 +98,8 @@ struct bpa_locus
   std::vector<int>      eigen_valid;  // locus->eigen_decomp_valid (locus.c:735)
   bool par_dirty = true, tips_dirty = true, weights_dirty = true, queued = false, alive = true;
   bool host_par_stale = false;        // bpa_plan_set_params_device moved the device block ahead of `par`
+  bool root_stale = false;            // a generic device sampler's steps left the root's CLV unstored (gs_mark_roots): nothing but the
+                                      // sampler may evaluate on this locus's buffers until a download has brought them level
   size_t code_bytes() const { return states == 4 ? 1 : 4; }
   bool needs_eigen() const { return !(dtype == BPA_DATA_DNA && model < BPA_DNA_MODEL_GTR); }   // locus.c:2426-2454
   std::unique_ptr<bpa_plan> scratch;  // single-locus calls reuse one small plan
@@ -146,6 +148,7 @@ struct bpa_engine
   // engine-level packing of the JC69 / one-category loci for step_jc69_v2_kernel (device_types.hpp): shared by all plans
   bool pack_dirty = true;               // a locus appeared / went away / changed its tip states or weights
   unsigned pack_epoch = 0;              // bumped when the slot numbering or a slot's shape changes: older plans fall back
+  unsigned stale_roots = 0;             // loci with root_stale set (0: roots_level has nothing to look at)
   std::vector<int32_t> slot_of;         // locus id -> slot (-1: not packed)
   std::vector<uint32_t> pack_shape;     // (locus id, np, tips) per slot, to detect a change of the numbering
   DevBuf<LaneStatic> d_lane_tab;
@@ -435,6 +438,21 @@ extern "C" void bpa_set_pattern_weights(bpa_locus_t * l, const unsigned * w)
 // asked for with the parameters it had THEN, so a setter lets the queue run before it changes them (the eager
 // semantics the header documents)
 static int run_queued(bpa_locus * l, bool want_lnl, unsigned root_clv, int root_scaler, double * lnl, bool persite);
+
+// The generic device sampler does not store the root's CLV in its steps (flags bit 11, gsampler_host.hpp: gs_skip_root_flag):
+// between bpa_sampler_iterate and the next download its loci's buffers are NOT what a step-by-step caller would hold.  The
+// single-locus calls, plans and batches that evaluate on such a locus fail instead of returning a number from a buffer
+// nobody wrote.  (One compare per call while no sampler has unstored roots.)
+static int roots_level(const bpa_engine * e, bpa_locus * const * loci, unsigned n, const char * who)
+{
+  if (!e->stale_roots) return 1;
+  for (unsigned i = 0; i < n; ++i)
+    if (loci[i] && loci[i]->root_stale)
+      return fail(std::string(who) + ": locus " + std::to_string(loci[i]->id) + " belongs to a device sampler that has iterated since its last download, and "
+                  "its steps do not store the root's CLV: call a sampler getter first (bpa_sampler_summary, bpa_sampler_get_tree, ...) - its "
+                  "download brings the loci's buffers level");
+  return 1;
+}
 static void settle_queue(bpa_locus * l)
 {
   if (l->pending && l->alive) (void)run_queued(l, false, 0, BPA_SCALE_BUFFER_NONE, nullptr, false);
@@ -728,6 +746,7 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
   if (!set_device(e)) return 0;
   const unsigned T = b->nloci;
   if (!T) return fail("plan: empty batch");
+  if (!roots_level(e, b->loci, T, "plan")) return 0;
   p->eng = e;
   p->bytes_partials = p->bytes_pmatrix = p->flops_partials = p->bytes_codes = 0; p->node_updates = p->pattern_updates = 0;     // (a plan object may be rebuilt)
   p->fused_klane = p->fused_jc69 = p->jc69_v2 = p->klane_v2 = false; p->fused_rt = 0;
@@ -1091,6 +1110,8 @@ static int plan_launch_mode(bpa_plan * p, int mode)
   // A/B switches of DESIGN.md's appendix, read once
   static const bool env_fused_split = BPA_EXP_SWITCH("BPA_FUSED_SPLIT") != nullptr;
   bpa_engine * e = p->eng;
+  if (e->stale_roots)                       // (a plan made before the sampler ran)
+    for (uint32_t id : p->h_locus) if (!roots_level(e, &e->loci[id], 1, "plan")) return 0;
   if (!flush(e)) return 0;
   PlanDev d = p->pd;
   d.loci = e->d_loci.p;
@@ -1392,6 +1413,9 @@ extern "C" int bpa_plans_launch(bpa_plan_t * const * plans, unsigned count)
   std::lock_guard<std::recursive_mutex> lock_(e->mtx);
   static const bool no_chain = BPA_EXP_SWITCH("BPA_NO_CHAIN") != nullptr;
   if (!e->usedata) return 1;
+  if (e->stale_roots)                       // (the chained launch below does not pass through plan_launch_mode)
+    for (unsigned k = 0; k < count; ++k)
+      for (uint32_t id : plans[k]->h_locus) if (!roots_level(plans[k]->eng, &plans[k]->eng->loci[id], 1, "plan")) return 0;
   unsigned i = 0;
   while (i < count)
   {
@@ -1568,6 +1592,7 @@ static double batch_now() { return std::chrono::duration<double>(std::chrono::st
 static int batch_begin_packed(bpa_engine * e, const bpa_batch_t * b, bool & handled, bool fast_ok = true)
 {
   handled = false;
+  if (b->loci && !roots_level(e, b->loci, b->nloci, "batch")) return 0;
   static const bool off = BPA_EXP_SWITCH("BPA_JC69_V1") != nullptr || BPA_EXP_SWITCH("BPA_NO_JC69_FAST") != nullptr;
   if (off || !b->root_clv || !b->nloci) return 1;
   if (!flush(e) || !engine_pack(e)) return 0;
@@ -1943,6 +1968,7 @@ static int requeue(bpa_locus * l, std::vector<unsigned> & pm, std::vector<double
 static int run_queued(bpa_locus * l, bool want_lnl, unsigned root_clv, int root_scaler, double * lnl, bool persite)
 {
   bpa_engine * e = l->eng;
+  if (!roots_level(e, &l, 1, "single-locus call")) return 0;
   // take the queue first: the paths below flush the engine, which must not see this locus as pending again
   std::vector<unsigned> pm; std::vector<double> len; std::vector<bpa_op_t> ops;
   pm.swap(l->pend_pm); len.swap(l->pend_len); ops.swap(l->pend_ops);

@@ -498,13 +498,21 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
 // BPA_GS_ROOTSTORE=1: every parent stored (A/B).
 static uint32_t gs_skip_root_flag(const bpa_sampler * s) { return s->env_rootstore ? 0u : 2048u; }
 static uint32_t gs_root_flag(const bpa_sampler * s) { return s->g_level_eval ? 0u : gs_skip_root_flag(s); }
+// ... and until that download the loci say so: a single-locus call, a plan or a batch on one of them fails (engine.hip:
+// roots_level) instead of reading a root buffer no step has written.  Marked once per run of steps, cleared by gs_level_roots.
+static void gs_mark_roots(bpa_sampler * s, bool stale)
+{
+  s->g_root_stale = stale;
+  for (bpa_locus * l : s->loci)
+    if (l->root_stale != stale) { l->root_stale = stale; if (stale) s->eng->stale_roots++; else s->eng->stale_roots--; }
+}
 
 // the step's likelihood: the engine's kernels over the records the step kernel wrote
 static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci step */)
 {
   bpa_engine * e = s->eng;
   if (!e->usedata) return 1;                       // lnL = 0 for every locus (the buffer was zeroed): the MSC prior
-  if (!s->g_alljc && !s->g_level_eval && gs_skip_root_flag(s)) s->g_root_stale = true;
+  if (!s->g_alljc && !s->g_level_eval && gs_skip_root_flag(s) && !s->g_root_stale) gs_mark_roots(s, true);
   if (s->g_s20)
   {
     // amino-acid loci: fresh P-matrices (pmatrix_wg2_kernel, one workgroup per entry, holes return at once), the tiled
@@ -1244,7 +1252,7 @@ static int gs_level_roots(bpa_sampler * s)
   s->g_level_eval = true;
   const int ok = gs_step(s, 5) && gs_eval(s, 1) && gs_step(s, 4);
   s->g_level_eval = false;
-  if (ok) s->g_root_stale = false;
+  if (ok) gs_mark_roots(s, false);
   return ok;
 }
 
