@@ -605,18 +605,24 @@ class Sampler:
         return dict(zip(self.FT_NAMES, pj)), dict(zip(self.FT_NAMES, ft))
 
     def burnin(self, iterations):
-        """`iterations` iterations with the program's step-length resets (after every quarter and at the end, method.c:5364)"""
+        """`iterations` iterations with the program's step-length resets (after every quarter and at the end, method.c:5364).
+        Runs on the persistent kernel and, with the program's moves (set_program_moves), on the generic and the big-tree
+        sampler; from 200 iterations on, a sampler without them fails before any iteration has run"""
         ft = (C.c_double * 5)()
         _chk(lib().bpa_sampler_burnin(self.h, int(iterations), ft))
         return dict(zip(self.FT_NAMES, ft))
 
     def set_proposal_kernel(self, kind):
-        """0 uniform windows on our streams (default), 1 BPP's legacy_rndu + Bactrian-Laplace (before initialize)"""
+        """0 uniform windows on our streams (default), 1 BPP's legacy_rndu + Bactrian-Laplace (before initialize).  Every
+        kind of sampler but the composite runs 1; the generic and the big-tree sampler (kind() 'generic' / 'big') only
+        together with set_program_moves and a theta prior — iterate raises otherwise"""
         _chk(lib().bpa_sampler_set_proposal_kernel(self.h, int(kind)))
 
     def set_program_moves(self, on, slide_prob=0.1):
         """THETA / TAU / MIX as the program runs them (BPP kernel): sliding window with probability slide_prob and the
-        metropolized Gibbs draw otherwise, thetas re-drawn inside the rubber-band and the mixing proposals"""
+        metropolized Gibbs draw otherwise, thetas re-drawn inside the rubber-band and the mixing proposals.  On the persistent
+        kernel, the generic sampler and the big-tree sampler (loci of more than 16 tips, scalers, unphased diploids); not on
+        a composite"""
         _chk(lib().bpa_sampler_set_program_moves(self.h, int(bool(on)), float(slide_prob)))
 
     def gibbs_counters(self):

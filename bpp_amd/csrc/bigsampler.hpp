@@ -13,6 +13,13 @@
 //     P-matrices, node updates + per-pattern terms, per-locus sums                     -> lnL per locus
 //     all-loci steps only: gsum_decide_kernel (sum of the per-locus terms, ONE decision)
 //
+// big_step_kernel<true> is the same step under BPP's proposal kernel (bpa_sampler_set_proposal_kernel): the locus's stream is
+// smp2::Stream<true> — the reference's generator, Bactrian-Laplace windows, its acceptance rule, nothing drawn for a proposal
+// that cannot be made (draw_window / skip_u / accept of a00_driver.c).  It runs with the program's THETA / TAU / MIX
+// (bpa_sampler_set_program_moves): TAU's window variate and MIX's factor come from the decisions' state on the device
+// (gsm::GDecState), a locus brings its Jacobian and TAU's three T2h, and gsm::gdec_kernel decides from the sums
+// (bigsampler_host.hpp: gb_iterate).  big_step_kernel<false> is the uniform-window step as it has always been.
+//
 // Reference: gtree.c:4585 (ages), 6531 (SPR), stree.c:5512 / 4338 (tau + rubber band), prop_mixing.c:52, gtree.c:3957.
 #pragma once
 
@@ -32,6 +39,7 @@ struct BTree                              // one per locus, in HBM (and its copy
   int32_t  root, tips;
   uint32_t proposals, accepted;
   uint32_t work_nupd, work_nbr, work_neval, pad_;
+  uint32_t pj_gage, pj_gage_acc, pj_gspr, pj_gspr_acc;     // per-locus proposals / acceptances by move type (bpa_sampler_adapt_finetune)
   int8_t   gl[MAXPOP];                    // gene tips below each population (never changes: tips stay in their species)
 };
 
@@ -42,6 +50,7 @@ struct BArgs
   uint32_t mode;                          // 0 GAGE k, 1 GSPR k, 2 TAU, 3 MIX, 4 settle (+ THETA statistics), 5 start-up evaluation
   uint32_t k;
   uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch), 3 commit (start-up)
+  uint32_t pend_mode;                     // pend == 1: the kind of the step being settled (0 GAGE, 1 GSPR)
   const double * lnl_new;                 // [T] lnL of the pending step's evaluation (task = locus)
   double * hast, * logpr_new;             // [T] Hastings term / proposed MSC density of the step being proposed
   double * delta;                         // [T] an all-loci step: this locus's density + Jacobian term
@@ -56,6 +65,11 @@ struct BArgs
   uint32_t tau_q; double tau_u, mix_c, mix_lnc;
   int8_t * pop_nc; double * pop_t2h;      // [MAXPOP][T] mode 4: the statistics the THETA kernel reads
   uint32_t refresh_logpr;
+  // the program's THETA / TAU / MIX (BPP's kernel, gsm::gdec_kernel decides): this step's window variate / factor lies in the
+  // decisions' state, a locus brings its Jacobian (delta) and, TAU, the T2h of q and its two children after the move
+  uint32_t prog;
+  const gsm::GDecState * dstep;
+  double * t2h3;                          // [T][3]
   Species sp;
 };
 
@@ -65,6 +79,7 @@ struct Work
   int nd[2*BN], br[BN], targets[BN], stack[BN];
   int gl[MAXPOP], nin[MAXPOP], nc[MAXPOP];
   double times[BN];
+  double o_t2h[MAXPOP]; int8_t o_nc[MAXPOP];            // the program's TAU: every population's T2h of the proposed tree
   unsigned char isbr[BN], isnd[BN];
   // a prune-and-regraft between its two lane-0 parts: what the scan of all nodes (64 lanes) needs and leaves
   int g_a, g_p, g_s, g_g, g_popt, g_popp, g_ok;
@@ -187,16 +202,26 @@ __device__ void swap_ids(BTree & t, int a, int b)
 #undef BIGM
 }
 
+// the locus's random stream as the proposal kernel draws from it (sweep2.hpp: ours, or — BPP — the reference's generator,
+// Bactrian-Laplace windows and acceptance rule, t.rng then holding the 32-bit legacy_rndu state)
+template <bool BPP> __device__ inline smp2::Stream<BPP> & stream(BTree & t)
+{
+  static_assert(sizeof(smp2::Stream<BPP>) == sizeof(a00_rng_t), "Stream is its state");
+  return *reinterpret_cast<smp2::Stream<BPP> *>(&t.rng);
+}
+
 // GSPR, lane 0's first part (gspr_step of a00_driver.c up to the target / source scans): the pruned node, the draws, the new
 // age of its father and the population it falls in
+template <bool BPP>
 __device__ void gspr_pre(const BArgs & A, BTree & t, const Species & sp, const double * s_tau, Work & W)
 {
+  smp2::Stream<BPP> & rng = stream<BPP>(t);
   const int n = 2*t.tips - 1;
   int a = -1, c = 0;
   for (int j = 0; j < n; ++j) if (j != t.root && c++ == (int)A.k) { a = j; break; }
   W.g_a = a; W.g_ok = 0;
   if (a < 0) return;
-  const double u1 = rndu(&t.rng) - 0.5, u2 = rndu(&t.rng);
+  const double u1 = rng.window(), u2 = rng.u();
   const int p = t.parent[a], s = t.left[p] == a ? t.right[p] : t.left[p], g = t.parent[p];
   // youngest population from a's upwards that holds gene tips outside a's subtree (gtree.c:6664-6669)
   const int leaves = count_tips(t, a, W.stack);
@@ -230,10 +255,13 @@ __device__ void gspr_scan(const BTree & t, const Species & sp, Work & W, const u
 }
 
 // ---- 4. propose (gage_step / gspr_step / tau_step / mix_step / a00_initialize of a00_driver.c, one locus), then 5. the records
+template <bool BPP>
 __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const Species & sp, const double * s_tau, const uint32_t MODE,
                             const double lminf, const double lmaxf, const double tq_old, const double tq_lo, const double tq_hi,
-                            const double minf, const double maxf, Work & W)
+                            const double minf, const double maxf, const double mix_c, const double mix_lnc, Work & W)
 {
+  smp2::Stream<BPP> & rng = stream<BPP>(t);
+  const bool prog = BPP && A.prog;
   const int n = 2*t.tips - 1;
   bool evaluate = false;
   int * br = W.br, * nd = W.nd, nb = 0, nn = 0;
@@ -249,12 +277,12 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
     for (int j = 0; j < n; ++j) if (t.left[j] >= 0 && c++ == (int)A.k) { v = j; break; }
     if (v >= 0)
     {
-      const double u = rndu(&t.rng) - 0.5;
+      const double u = rng.window();
       const int l = t.left[v], r = t.right[v], p = t.parent[v];
       double lo = fmax(t.time[l], t.time[r]);
       if (t.pop[l] != t.pop[r]) lo = fmax(lo, s_tau[lca_pop(sp, t.pop[l], t.pop[r])]);
       const double hi = p >= 0 ? t.time[p] : 999.0;
-      if (!(hi > lo)) (void)rndu(&t.rng);
+      if (!(hi > lo)) rng.skip();
       else
       {
         
@@ -282,7 +310,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
         for (int h = 0; h < 2; ++h)
           for (unsigned long long m = W.g_tmask[h]; m; m &= m - 1) { const int j = 64*h + __ffsll((long long)m) - 1; targets[ntg++] = j == p ? s : j; }
       if (p != t.root) nsrc += __popcll(W.g_smask[0]) + __popcll(W.g_smask[1]);
-      if (!ntg) (void)rndu(&t.rng);
+      if (!ntg) rng.skip();
       else
       {
         int tgt = targets[(int)(u2*ntg) % ntg];
@@ -333,9 +361,17 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
       isbr[t.left[k]] = isbr[t.right[k]] = 1; if (t.parent[k] >= 0) isbr[k] = 1;
       for (int v = k; v >= 0; v = t.parent[v]) isnd[v] = 1;
     }
-    const double lp_new = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
+    const double lp_new = prog ? tree_logpr(t, sp, s_tau, W.o_nc, W.o_t2h, 1, W) : tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
     A.logpr_new[i] = lp_new;
-    A.delta[i] = ((lp_new - t.logpr) + below*lminf) + above*lmaxf;
+    if (prog)
+    {
+      // (tau_step of a00_driver.c, program: the densities' change follows from the sums; a tree that does not fit the proposed
+      //  species tree reaches them as an unusable term)
+      const int aff[3] = { q, cl, cr };
+      for (int j = 0; j < 3; ++j) A.t2h3[(size_t)3*i + j] = lp_new == lp_new ? W.o_t2h[aff[j]] : __longlong_as_double(0x7ff8000000000000ll);
+      A.delta[i] = below*lminf + above*lmaxf;
+    }
+    else A.delta[i] = ((lp_new - t.logpr) + below*lminf) + above*lmaxf;
     A.lnl_cur[i] = t.lnl;
     if (above + below)
     {
@@ -350,7 +386,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
     int ninner = 0;
     for (int k = 0; k < n; ++k)
     {
-      if (t.left[k] >= 0) { if (MODE == 3) t.time[k] *= A.mix_c; nd[nn++] = k; ++ninner; }
+      if (t.left[k] >= 0) { if (MODE == 3) t.time[k] *= mix_c; nd[nn++] = k; ++ninner; }
       if (t.parent[k] >= 0) br[nb++] = k;
     }
     if (MODE == 5)
@@ -360,7 +396,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
     }
     const double lp_new = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
     A.logpr_new[i] = lp_new;
-    A.delta[i] = (lp_new - t.logpr) + (double)ninner*A.mix_lnc;
+    A.delta[i] = (prog && MODE == 3) ? (double)ninner*mix_lnc : (lp_new - t.logpr) + (double)ninner*mix_lnc;
     A.lnl_cur[i] = t.lnl;
     install(t, br, nb, nd, nn);
     evaluate = true;
@@ -407,6 +443,7 @@ __device__ inline void copy_nodes(BTree & dst, const BTree & src, uint32_t lane)
   if (lane == 0) { dst.root = src.root; dst.tips = src.tips; }
 }
 
+template <bool BPP = false>
 __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
 {
   __shared__ double s_tau[3*MAXPOP];
@@ -440,9 +477,10 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
       {
         const double lnl = A.lnl_new[i], lp_new = A.logpr_new[i];
         const double lnacc = (lp_new - t.logpr) + (lnl - t.lnl) + A.hast[i];
-        const double u = rndu(&t.rng);
+        const bool acc = stream<BPP>(t).accept(lnacc);
         t.proposals++;
-        if (lnacc >= 0 || u < exp(lnacc)) { t.lnl = lnl; t.logpr = lp_new; t.accepted++; }
+        if (A.pend_mode == 0) { t.pj_gage++; t.pj_gage_acc += acc ? 1u : 0u; } else { t.pj_gspr++; t.pj_gspr_acc += acc ? 1u : 0u; }
+        if (acc) { t.lnl = lnl; t.logpr = lp_new; t.accepted++; }
         else back = true;
       }
     }
@@ -463,11 +501,13 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
 
   // ---- 3. the proposed species tree of an all-loci step is this workgroup's copy of the taus
   double lminf = 0, lmaxf = 0, tq_old = 0, tq_lo = 0, tq_hi = 0, minf = 1, maxf = 1;
+  const bool prog = BPP && A.prog;
+  const double mix_c = (prog && MODE == 3) ? A.dstep->mix_c : A.mix_c, mix_lnc = (prog && MODE == 3) ? A.dstep->mix_lnc : A.mix_lnc;
   if (MODE == 2)
   {
     const int q = (int)A.tau_q, pq = sp.parent[q];
     tq_old = s_tau[q]; tq_lo = fmax(s_tau[sp.left[q]], s_tau[sp.right[q]]); tq_hi = pq >= 0 ? s_tau[pq] : 999.0;
-    const double tnew = reflect(tq_old + sp.ft_tau*(A.tau_u - 0.5), tq_lo, tq_hi);
+    const double tnew = reflect(tq_old + sp.ft_tau*(prog ? A.dstep->tau_w : A.tau_u - 0.5), tq_lo, tq_hi);
     minf = (tnew - tq_lo)/(tq_old - tq_lo); maxf = (tnew - tq_hi)/(tq_old - tq_hi);
     lminf = log(minf); lmaxf = log(maxf);
     __syncthreads();
@@ -476,7 +516,7 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
   }
   else if (MODE == 3)
   {
-    if (lane < (uint32_t)sp.npop) s_tau[lane] *= A.mix_c;
+    if (lane < (uint32_t)sp.npop) s_tau[lane] *= mix_c;
     __syncthreads();
   }
   // the state a rejection comes back to (every proposing mode; a step that proposes nothing for this locus never reads it)
@@ -484,12 +524,12 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
   __syncthreads();
   if (MODE == 1)
   {
-    if (lane == 0) gspr_pre(A, t, sp, s_tau, s_w);
+    if (lane == 0) gspr_pre<BPP>(A, t, sp, s_tau, s_w);
     __syncthreads();
     if (s_w.g_ok) gspr_scan(t, sp, s_w, lane);
     __syncthreads();
   }
-  if (lane == 0) big_propose(A, i, t, sp, s_tau, MODE, lminf, lmaxf, tq_old, tq_lo, tq_hi, minf, maxf, s_w);
+  if (lane == 0) big_propose<BPP>(A, i, t, sp, s_tau, MODE, lminf, lmaxf, tq_old, tq_lo, tq_hi, minf, maxf, mix_c, mix_lnc, s_w);
   __syncthreads();
   {
     const uint32_t * tsrc = reinterpret_cast<const uint32_t *>(&s_t);

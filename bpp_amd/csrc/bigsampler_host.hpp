@@ -53,8 +53,8 @@ static int gb_upload(bpa_sampler * s)
   HIPCHK(hipMemsetAsync(s->g_delta.p, 0, T*sizeof(double), e->stream));
   HIPCHK(hipMemsetAsync(s->g_active.p, 0, T, e->stream));
   if (s->allreduce) return fail("bpa_sampler: the big-tree sampler runs on one rank (a handful of loci: nothing to shard)");
-  s->epoch = 0; s->mix_pending = false; s->g_pend = 0;
-  s->uploaded = true;
+  s->epoch = 0; s->mix_pending = false; s->g_pend = 0; s->g_pend_mode = 0;
+  s->uploaded = true; s->gp_mirror = false;           // (the program's moves: the decisions' state goes to the device again, gs_prog_ready)
   return 1;
 }
 
@@ -64,17 +64,21 @@ static int gb_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   bpa_engine * e = s->eng;
   gbig::BArgs a{};
   a.trees = s->b_dev.p; a.undo = s->b_undo.p; a.T = s->nloci; a.mode = mode; a.k = k;
-  a.pend = s->g_pend; a.lnl_new = s->g_lnl.p; a.hast = s->g_hast.p; a.logpr_new = s->g_logpr.p; a.delta = s->g_delta.p;
+  a.pend = s->g_pend; a.pend_mode = s->g_pend_mode; a.lnl_new = s->g_lnl.p; a.hast = s->g_hast.p; a.logpr_new = s->g_logpr.p; a.delta = s->g_delta.p;
   a.active = s->g_active.p; a.flag = s->flag.p; a.epoch = s->epoch; a.lnl_cur = s->g_lnlcur.p;
   a.ops = s->g_ops20.p; a.op_rng = s->g_oprng.p; a.root_clv = s->g_root20.p; a.root_scaler = s->g_rscaler.p;
   a.mat_task = s->g_mtask.p; a.mat_pm = s->g_mpm.p; a.mat_length = s->g_len.p; a.maxmat = s->g_maxmat; a.maxops = s->g_maxops;
   a.taus = s->taus.p; a.tau_q = k; a.tau_u = tau_u; a.mix_c = mix_c; a.mix_lnc = mix_lnc;
   a.pop_nc = s->pop_nc.p; a.pop_t2h = s->pop_t2h.p;
   a.refresh_logpr = s->logpr_stale ? 1u : 0u; s->logpr_stale = false;
+  a.prog = gs_prog(s) ? 1u : 0u; a.dstep = s->g_dst.p; a.t2h3 = s->g_t2h3.p;
   a.sp = s->sp;
-  hipLaunchKernelGGL(gbig::big_step_kernel, dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);       // one workgroup per locus
+  // one workgroup per locus; BPP's proposal kernel is the other instantiation
+  if (s->kernel_bpp) hipLaunchKernelGGL((gbig::big_step_kernel<true>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
+  else hipLaunchKernelGGL((gbig::big_step_kernel<false>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
   HIPCHK(hipGetLastError());
   s->launches++;
+  s->g_pend_mode = mode;
   s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : 0u;
   return 1;
 }
@@ -121,10 +125,29 @@ static int gb_decide(bpa_sampler * s, double uacc, int tau_q, double win_u, doub
 
 static int gb_initialize(bpa_sampler * s) { return gb_step(s, 5) && gb_eval(s, 1); }
 
+// an all-loci step of the program's moves, decided on the device (gs_dev_allloci of gsampler_host.hpp with this sampler's
+// step and evaluation): proposal from the decisions' state, likelihood, the loci's sums, gdec_kernel — nothing waits for the host
+static int gb_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
+{
+  bpa_engine * e = s->eng;
+  const bool mix = q < 0;
+  if (!gb_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !gb_eval(s, 1)) return 0;
+  hipLaunchKernelGGL(gsm::gdec_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
+                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p);
+  HIPCHK(hipGetLastError());
+  s->launches++;
+  s->epoch++;
+  s->logpr_stale = true;             // (an accepted step re-drew thetas; the host does not know the decision: every density is taken again)
+  return mix ? gs_dec_launch<2>(s, -1, -1) : gs_dec_launch<1>(s, q, q + 1);
+}
+
 static int gb_iterate(bpa_sampler * s, unsigned iterations)
 {
   bpa_engine * e = s->eng;
   s->host_current = false;
+  const bool prog = gs_prog(s);
+  if (s->kernel_bpp && !prog) return fail("bpa_sampler: on the big-tree sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
+  if (prog && !gs_prog_ready(s)) return 0;
   for (unsigned it = 0; it < iterations; ++it)
   {
     const unsigned ngage = s->env_gage >= 0 ? (unsigned)s->env_gage : s->maxtips - 1, ngspr = s->env_gspr >= 0 ? (unsigned)s->env_gspr : 2*s->maxtips - 2;   // (BPA_SMP_STEPS: diagnostics)
@@ -132,6 +155,20 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
     for (unsigned k = 0; k < ngspr; ++k)   { if (!gb_step(s, 1, k) || !gb_eval(s, 0)) return 0; }
     s->sweeps++;
     if (s->env_nomix) continue;
+    if (prog)
+    {
+      // THETA / TAU / MIX as the program runs them (gs_iterate's device-decided branch): the host is paced two iterations behind
+      // its own launches and waits for nothing else
+      if (s->gp_pace_n >= 2) HIPCHK(hipEventSynchronize(s->gp_pace[(s->gp_pace_n - 2) & 3u]));
+      if (!gb_step(s, 4) || !gs_dev_theta(s)) return 0;
+      for (int q = s->sp.S; q < s->sp.npop; ++q) if (!gb_dev_allloci(s, q)) return 0;
+      if (!gb_dev_allloci(s, -1)) return 0;
+      hipEvent_t & ev = s->gp_pace[s->gp_pace_n & 3u];
+      if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      HIPCHK(hipEventRecord(ev, e->stream));
+      s->gp_pace_n++;
+      continue;
+    }
     if (s->sp.theta_alpha > 0)
     {
       if (!gb_step(s, 4)) return 0;
@@ -159,7 +196,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
 static int gb_download(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
-  if (!gb_step(s, 4)) return 0;
+  if (!gb_step(s, 4) || !gs_prog_pull(s)) return 0;
   HIPCHK(hipMemcpyAsync(s->b_trees.data(), s->b_dev.p, s->nloci*sizeof(gbig::BTree), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 1;

@@ -763,7 +763,7 @@ static void gs_declog(const char * what, int k, double lnacc, int acc)
 // between the sum kernel and gdec_kernel (gs_dev_allreduce): with a stream-ordered collective (RCCL) no host waits for anything
 static bool gs_prog_dev_wanted(const bpa_sampler * s)
 {
-  return !s->env_hostdec;
+  return s->big || !s->env_hostdec;           // (the big-tree sampler has the device form only)
 }
 
 // the device's counters by move type and its copy of the global stream come back to the host's (adapt_finetune, a download)

@@ -1439,10 +1439,9 @@ extern "C" int bpa_sampler_set_proposal_kernel(bpa_sampler_t * s, int kind)
   if (s->comp) return 1;
   if (kind != BPA_KERNEL_UNIFORM && kind != BPA_KERNEL_BPP) return fail("bpa_sampler_set_proposal_kernel: BPA_KERNEL_UNIFORM or BPA_KERNEL_BPP");
   if (s->uploaded) return fail("bpa_sampler_set_proposal_kernel: before bpa_sampler_initialize (as a00_set_proposal_kernel)");
-  if (s->big && kind == BPA_KERNEL_BPP) return fail("bpa_sampler_set_proposal_kernel: BPP's kernel runs in the persistent iteration kernel and in the generic sampler (loci of <= 16 tips)");
   s->kernel_bpp = kind == BPA_KERNEL_BPP;
-  // (the generic sampler: together with bpa_sampler_set_program_moves and a theta prior — checked when the run starts)
-  for (unsigned i = 0; i < s->nloci; ++i) (s->generic ? s->g_trees[i].rng : s->h_trees[i].rng) = stream_seed(s, stream_of(s, i));
+  // (the generic and the big-tree sampler: together with bpa_sampler_set_program_moves and a theta prior — checked when the run starts)
+  for (unsigned i = 0; i < s->nloci; ++i) (s->big ? s->b_trees[i].rng : s->generic ? s->g_trees[i].rng : s->h_trees[i].rng) = stream_seed(s, stream_of(s, i));
   s->grng = stream_seed(s, A00_GLOBAL_STREAM);
   s->v2_grng_sent = false;
   return 1;
@@ -1906,13 +1905,17 @@ static int sampler_pool_counts(bpa_sampler * s, unsigned long long * c, unsigned
 extern "C" int bpa_sampler_adapt_finetune(bpa_sampler_t * s, double * pjump, double * finetune)
 {
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
-  if (s->comp || s->big) return fail("bpa_sampler_adapt_finetune: the move-type counters are the persistent iteration kernel's and the generic sampler's (with the program's moves)");
+  if (s->comp) return fail("bpa_sampler_adapt_finetune: the move-type counters are the persistent iteration kernel's, the generic sampler's and the big-tree sampler's (those two with the program's moves)");
+  // (checked before the download, which settles a step: a sampler that cannot adapt is left as it is)
+  const char * const needs_prog = "bpa_sampler_adapt_finetune: on a generic or big-tree sampler the step-length rule runs with the program's moves (bpa_sampler_set_program_moves)";
+  if (s->big && !(s->kernel_bpp && s->sp.program_moves)) return fail(needs_prog);
   if (!sampler_download(s)) return 0;                 // (settles the launches in flight; the counters are then final)
-  if (s->generic)
+  if (s->generic || s->big)
   {
-    if (!(s->kernel_bpp && s->sp.program_moves)) return fail("bpa_sampler_adapt_finetune: on a generic sampler the step-length rule runs with the program's moves (bpa_sampler_set_program_moves)");
+    if (!(s->kernel_bpp && s->sp.program_moves)) return fail(needs_prog);
     unsigned long long tot[4] = {0, 0, 0, 0};          // gage proposed / accepted, gspr proposed / accepted over all loci
-    for (const auto & t : s->g_trees) { tot[0] += t.pj_gage; tot[1] += t.pj_gage_acc; tot[2] += t.pj_gspr; tot[3] += t.pj_gspr_acc; }
+    if (s->big) for (const auto & t : s->b_trees) { tot[0] += t.pj_gage; tot[1] += t.pj_gage_acc; tot[2] += t.pj_gspr; tot[3] += t.pj_gspr_acc; }
+    else for (const auto & t : s->g_trees) { tot[0] += t.pj_gage; tot[1] += t.pj_gage_acc; tot[2] += t.pj_gspr; tot[3] += t.pj_gspr_acc; }
     unsigned long long c[10];
     for (int k = 0; k < 4; ++k) { if (tot[k] < s->gp_pj_base[k]) s->gp_pj_base[k] = 0;      /* (the trees were set again: their counts start over) */
                                   c[k] = tot[k] - s->gp_pj_base[k]; s->gp_pj_base[k] = tot[k]; }
@@ -1974,9 +1977,9 @@ extern "C" int bpa_sampler_burnin(bpa_sampler_t * s, unsigned iterations, double
   // what the rule needs is checked BEFORE the chain moves (a sampler that cannot adapt must not be left half-way through)
   if (iterations >= 200)
   {
-    if (s->comp || s->big) return fail("bpa_sampler_burnin: the step-length rule runs on the persistent iteration kernel and on the generic sampler with the program's moves (not on loci of several kinds or of more than 16 tips)");
-    if (s->generic && !(s->kernel_bpp && s->sp.program_moves)) return fail("bpa_sampler_burnin: on a generic sampler the step-length rule runs with the program's moves (bpa_sampler_set_program_moves)");
-    if (!s->generic)
+    if (s->comp) return fail("bpa_sampler_burnin: the step-length rule runs on the persistent iteration kernel and, with the program's moves, on the generic and the big-tree sampler (not on loci of several kinds)");
+    if ((s->generic || s->big) && !(s->kernel_bpp && s->sp.program_moves)) return fail("bpa_sampler_burnin: on a generic or big-tree sampler the step-length rule runs with the program's moves (bpa_sampler_set_program_moves)");
+    if (!s->generic && !s->big)
     {
       std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
       if (!set_device(s->eng) || !sampler_upload(s)) return 0;           // (which kernel runs the loci is settled at upload)

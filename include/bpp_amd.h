@@ -319,10 +319,11 @@ void bpa_sampler_set_finetune(bpa_sampler_t *, double gage, double gspr, double 
    since the last reset, and at i = 0 — 400: after 100 / 200 / 300 / 400 iterations, 300: after 150 / 300, 402: after 102 / 202 /
    302 / 402; below 200 iterations the program resets nothing and neither does this); bpa_burnin_schedule writes those points
    (at most cap of them) and returns their number.  finetune (5, may be null) receives the step lengths the burn-in ends with.
-   A sampler the rule cannot run on (loci of several kinds, the big-tree sampler, a generic sampler without the program's moves)
+   A sampler the rule cannot run on (loci of several kinds, a generic or big-tree sampler without the program's moves)
    fails BEFORE any iteration has run.
-   Where: the persistent iteration kernel (device counters by move type) and the generic sampler with the program's moves
-   (the trees carry the age / prune-regraft counts, the host its own decisions').  Several ranks: the per-locus moves' counts
+   Where: the persistent iteration kernel (device counters by move type), and the generic and the big-tree sampler with the
+   program's moves (the trees carry the age / prune-regraft counts, the decisions' state on the device — or, BPA_GS_HOSTDEC,
+   the host — those of tau, mixing and the theta window).  Several ranks: the per-locus moves' counts
    are pooled over the ranks first (the callback, or the mailboxes' one-shot exchange), so every rank ends at the same step
    lengths, the whole data set's — every rank calls it at the same point of its run.                                      */
 double bpa_finetune_onestep(double pjump, double finetune);
@@ -335,8 +336,11 @@ unsigned bpa_burnin_schedule(unsigned burnin, unsigned * after, unsigned cap);
                       legacy_rnd_symmetrical (random.c:192-238) for the ages, taus and thetas, acceptance "lnacc >= -1e-10 or
                       rndu < exp(lnacc)" with the number drawn only when needed (gtree.c:5476, stree.c:6286): the finetunes
                       then mean what they mean in a BPP control file.  Same trajectory as the host driver with
-                      A00_KERNEL_BPP.  The persistent iteration kernel, and (round 5) the generic sampler — there together
-                      with bpa_sampler_set_program_moves and a theta prior; not the big-tree sampler (bpa_sampler_kind).  */
+                      A00_KERNEL_BPP.  Every device sampler runs it (bpa_sampler_kind): the persistent iteration kernel, the
+                      generic sampler and the big-tree sampler (more than 16 tips, scale buffers, unphased diploids).  On
+                      the last two it comes together with bpa_sampler_set_program_moves and a theta prior: with BPP's
+                      kernel but without either of those, bpa_sampler_iterate fails with a message that names
+                      bpa_sampler_set_program_moves — no fall-back to the uniform windows.                              */
 #define BPA_KERNEL_UNIFORM 0
 #define BPA_KERNEL_BPP     1
 int  bpa_sampler_set_proposal_kernel(bpa_sampler_t *, int kind);
@@ -351,7 +355,10 @@ int  bpa_sampler_set_proposal_kernel(bpa_sampler_t *, int kind);
    <= 16 tips) takes the decision ON THE DEVICE since round 6 — one wave (gsm::gdec_kernel) runs the persistent kernel's
    control-wave functions on the loci's sums, installs the decision and makes the coming step's species-tree proposal: no host
    synchronisation inside an iteration (several ranks: the sums pass through the all-reduce callback on the stream first, so
-   with a stream-ordered collective none either).  BPA_GS_HOSTDEC=1 keeps round 5's form:
+   with a stream-ordered collective none either).  The big-tree sampler (up to 64 tips, scalers, diploid loci; one rank) does
+   the same with its own step kernel (gbig::big_step_kernel<true>): the loci bring their Jacobian and, for TAU, the T2h of the
+   three populations after the move; it has the device-decided form only.  BPA_GS_HOSTDEC=1 keeps round 5's form on the
+   generic sampler:
    the sums come to the HOST — 24 to 72 bytes and one synchronisation per all-loci step — which takes the
    decision with the statements of a00_driver.c (theta_step_gibbs / tau_step / mix_step) and sends it back as a one-lane
    launch.  With an all-reduce callback (several ranks) every rank's host decides from the sums over ALL ranks' loci: they go
