@@ -26,6 +26,21 @@ those that pass by the 5e-16 absolute bar instead; logpr was 0.0 in every case, 
   big, 24 tips with scalers             50    12  0.49   2.9e-16   2.9e-16      0.0       0       1.1e-16
   big, frogs (diploid)                  30     5  0.44   0.0       0.0          0.0       0       0.0
   composite                            100   133  0.60   1.1e-16   1.1e-16      2.0e-16   4       1.1e-16
+  at the samplers' pattern- and tip-count limits (tests/test_gpu_sampler_limits.py, loci of exact shape; uniform / program's moves):
+  persistent, 4-tip form, 1-64 patterns 200    40  0.69   1.7e-16   1.7e-16      0.0       6       1.1e-16
+  persistent, 8-tip form, 1-64 patterns 200    23  .59-.64  2.1e-16 2.1e-16      0.0       6       1.1e-16
+  persistent, 2-8 tips in one sampler  200    24  .65-.77  3.5e-16 3.5e-16      0.0       3       1.1e-16
+  generic, 4 tips, one 65-pattern locus 200    40  .69-.71  1.5e-16 1.5e-16      0.0       6       1.1e-16
+  composite, 64 / 65 patterns + GTR+G4 200   134  0.53   5.5e-16   5.5e-16      6.4e-16   6       1.1e-16
+  generic, 16 tips, JC69 1-255 patterns 200     4  .52-.57  2.0e-16 2.0e-16      0.0       5       1.1e-16
+    ... GTR+G4, 252 lanes, param. moves 200     5  .26-.57  1.4e-16 1.4e-16      0.0       8       4.4e-16
+    ... GTR, 3 categories, 255 lanes   200     5  .55-.57  1.3e-16 1.3e-16      0.0       8       0.0
+    ... GTR, 8 categories, 248 lanes   200     5  .55-.63  1.8e-16 1.8e-16      0.0       5       0.0
+    ... 12 and 16 tips side by side    200     6  .55-.60  0.0       0.0          0.0       3       0.0
+  big, 17 tips, 30 / 300 patterns       30     3  .30-.50  0.0       0.0          0.0       0       0.0
+  big, 64 tips, 30 / 300 patterns       30     3  .25-.47  0.0       0.0          0.0       0       1.1e-16
+  (generic: BPA_GS_CHAIN=0 and 1 gave the same figures; big: with and without scale buffers gave the same figures, and no scale
+  counter of the oracle's recompute was non-zero at 17 or 64 tips on these loci)
 
 No invariant failed on the device.  Reads between iterations (the last test): on the library before the marks of
 gs_mark_roots, all 180 reads (60 loci x single-locus call / plan / batch) of the buffer the tree then named as the root's returned
