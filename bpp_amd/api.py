@@ -103,6 +103,7 @@ def lib():
         "bpa_locus_get_scaler": (i, [vp, u, up]),
         "bpa_locus_set_scaler": (i, [vp, u, up]),
         "bpa_locus_get_eigen": (i, [vp, u, dp, dp, dp]),
+        "bpa_locus_get_category_rates": (i, [vp, dp]),
         "bpa_plan_create": (vp, [vp, C.POINTER(Batch)]),
         "bpa_plan_destroy": (None, [vp]),
         "bpa_plan_set_lengths": (i, [vp, dp]),
@@ -188,7 +189,7 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_experimental_build", "bpa_devi
             "bpa_core_update_pmatrix", "bpa_update_eigen", "bpa_compute_gamma_cats",
             "bpa_compress_site_patterns", "bpa_locus_get_clv", "bpa_locus_set_clv",
             "bpa_locus_get_pmatrix", "bpa_locus_set_pmatrix", "bpa_locus_get_scaler", "bpa_locus_set_scaler",
-            "bpa_locus_get_eigen", "bpa_plan_create", "bpa_plan_destroy", "bpa_plan_set_lengths",
+            "bpa_locus_get_eigen", "bpa_locus_get_category_rates", "bpa_plan_create", "bpa_plan_destroy", "bpa_plan_set_lengths",
             "bpa_plan_launch", "bpa_plan_get_lnl", "bpa_plan_lnl_device", "bpa_batch_evaluate", "bpa_batch_begin", "bpa_batch_fill", "bpa_batch_end", "bpa_batch_end_async", "bpa_batch_wait",
             "bpa_plan_enable_sum", "bpa_plan_enable_partial_sums", "bpa_plan_get_sum",
             "bpa_p2p_create", "bpa_p2p_connect", "bpa_p2p_allreduce", "bpa_p2p_status", "bpa_p2p_destroy", "bpa_p2p_set_timeout", "bpa_plans_launch_exchange", "bpa_plans_launch",
@@ -444,6 +445,12 @@ class Locus:
         ev, iev, evals = np.zeros((S, S)), np.zeros((S, S)), np.zeros(S)
         _chk(lib().bpa_locus_get_eigen(self.h, index, _dp(ev), _dp(iev), _dp(evals)))
         return ev, iev, evals
+
+    def get_category_rates(self):
+        """the category rates the device holds for this locus (a device sampler's alpha move writes them there)"""
+        out = np.zeros(self.rate_cats)
+        _chk(lib().bpa_locus_get_category_rates(self.h, _dp(out)))
+        return out
 
 
 # ---------------------------------------------------------------------------

@@ -2253,6 +2253,15 @@ extern "C" int bpa_locus_get_eigen(bpa_locus_t * l, unsigned index, double * eve
   return 1;
 }
 
+extern "C" int bpa_locus_get_category_rates(bpa_locus_t * l, double * out)
+{
+  std::lock_guard<std::recursive_mutex> lock_(l->eng->mtx);
+  if (!sync_for_access(l)) return 0;
+  const unsigned R = l->rate_cats;
+  HIPCHK(hipMemcpy(out, l->dev.par + par_rates(R), R*8, hipMemcpyDeviceToHost));
+  return 1;
+}
+
 // ------------------------------------------------ library-form entry points ---
 extern "C" int bpa_core_update_pmatrix(bpa_engine_t * e, double ** pmatrix, unsigned states,
                                        unsigned rate_cats, const double * rates,

@@ -1,8 +1,12 @@
 // gamma_dev.hpp — pll_compute_gamma_cats (gamma.c:221-284, mean mode) on the DEVICE: the generic sampler's alpha move
 // (gsampler.hpp; prop_gamma.c:93) turns a proposed shape into category rates without a host round trip.  The same
 // published routines in the same evaluation order as csrc/host_math.cpp (Pike & Hill 1966 Alg. 291; Bhattacharjee 1970
-// AS 32; Best & Roberts 1975 AS 91; Odeh & Evans 1974 AS 70) — device exp / log / pow differ from glibc's in the last
-// place, so the rates agree with bpa_compute_gamma_cats to ~1e-15 relative, not to the bit.
+// AS 32; Best & Roberts 1975 AS 91; Odeh & Evans 1974 AS 70) — on the same libm the two copies give the same bits
+// (tests/test_gamma_dev_host.py compiles this file as host code); device exp / log / pow differ from glibc's in the last
+// place, and how far that moves a rate depends on the shape: +-1 ulp on every exp / log / pow moves a rate by 1e-14 .. 6e-14
+// relative for 0.08 <= alpha <= 5, by 2e-13 .. 5e-13 for alpha <= 0.02, by 3e-13 .. 3e-12 at alpha = 100 and 2e-12 .. 1.3e-11 at
+// alpha = 500 (2 .. 8 categories; tests/golden/gamma_dev_sensitivity.json).  tests/test_gpu_subst_edges.py holds the device's
+// rates to 8 x those figures.
 #pragma once
 
 namespace gdev {

@@ -193,6 +193,9 @@ int  bpa_locus_get_scaler(bpa_locus_t *, unsigned scaler_index, unsigned * out);
 int  bpa_locus_set_scaler(bpa_locus_t *, unsigned scaler_index, const unsigned * in);
 int  bpa_locus_get_eigen(bpa_locus_t *, unsigned index, double * eigenvecs,
                          double * inv_eigenvecs, double * eigenvals);
+/* the [rate_cats] category rates the DEVICE holds for the locus (what bpa_set_category_rates uploaded, or what a device
+   sampler's alpha move last wrote there): read-only test access, as bpa_locus_get_eigen */
+int  bpa_locus_get_category_rates(bpa_locus_t *, double * out);
 
 /* ------------------------------------------------- batched update (N loci) --- */
 /* One proposal step for many loci in a single fused launch sequence: for locus

@@ -52,14 +52,14 @@ def msc_recompute(t, tips, species_parent, taus, thetas, tip_species):
         drv.close()
 
 
-def oracle_locus(d, model, R, scaling, params):
+def oracle_locus(d, model, R, scaling, params, rates=None):
     model = d.get("model", "jc69") if model is None else model
     R = d.get("rate_cats", 1) if R is None else R
     S = d.get("states", 4)
     if params is not None:
         f, q, a = params
         return O.OracleLocus(S, R, d["seqs"], d["weights"], model=model, freqs=np.asarray(f, float), qrates=np.asarray(q, float),
-                             rates=bpp_amd.compute_gamma_cats(a, a, R), scaling=scaling)
+                             rates=bpp_amd.compute_gamma_cats(a, a, R) if rates is None else rates, scaling=scaling)
     return O.OracleLocus(S, R, d["seqs"], d["weights"], model=model, freqs=None if model == "jc69" else d["freqs"],
                          qrates=None if model == "jc69" else d["exch"], rates=d.get("rates"), scaling=scaling)
 
@@ -77,11 +77,15 @@ def total_lnl(drv):
     return drv.summary()["total_lnl"] if hasattr(drv, "summary") else drv.total_lnl()
 
 
-def check_state(drv, data, species_parent, tip_species=None, model=None, R=None, scaling=False, loci=None, subst=None, worst=None):
+def check_state(drv, data, species_parent, tip_species=None, model=None, R=None, scaling=False, loci=None, subst=None, worst=None,
+                rates_of=None):
     """Assert every invariant on every locus; returns the largest differences seen (also merged into `worst` when given):
     dict(lnl, logpr, total, root_buffer, pmat_ulps, pmat_abs).  model / R: None = each locus's own (data[i]["model"],
     ["rate_cats"]); subst: the loci's substitution parameters move — the oracle takes drv.get_subst_model(i); loci: the
-    engine loci the sampler was built on — their buffers are read too (after the getters, which download)."""
+    engine loci the sampler was built on — their buffers are read too (after the getters, which download); rates_of (with
+    subst): locus number -> the category rates the oracle takes instead of the host routine's for the locus's alpha, or None
+    for the host routine's — the DEVICE's own (Locus.get_category_rates) for the loci whose alpha is so large that their last
+    places, held to their own bar by the caller, reach a P-matrix entry beyond the P-matrix bar."""
     n = len(data)
     taus, thetas = [float(x) for x in drv.taus()], [float(x) for x in drv.thetas()]
     par = _ints(species_parent)
@@ -162,7 +166,7 @@ def check_state(drv, data, species_parent, tip_species=None, model=None, R=None,
         seen["logpr"] = max(seen["logpr"], e)
         assert e < LOGPR_TOL, f"locus {i} logpr: held {t['logpr']!r}, recomputed {want_logpr!r} (rel {e:.3e})"
         # 6. likelihood
-        ol = oracle_locus(d, model, R, scaling, drv.get_subst_model(i) if subst else None)
+        ol = oracle_locus(d, model, R, scaling, drv.get_subst_model(i) if subst else None, rates_of(i) if subst and rates_of else None)
         full = ol.full_lnl(left, right, time, root)
         if d.get("diploid") is not None:
             full = oracle_root_term(ol, d, ol.clv[root], ol.scaler[root])

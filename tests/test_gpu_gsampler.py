@@ -17,7 +17,8 @@ from common import rel
 pytestmark = pytest.mark.gpu
 
 
-def walk(host, dev, iters, nloci, check_every=1, tol=1e-12):
+def walk(host, dev, iters, nloci, check_every=1, tol=1e-12, each=None):
+    """each: called with the iteration's number after every checked iteration (a test's own per-iteration checks)"""
     host.initialize(); dev.initialize()
     s = dev.summary()
     assert rel(s["total_lnl"], host.total_lnl()) < 1e-13
@@ -29,6 +30,8 @@ def walk(host, dev, iters, nloci, check_every=1, tol=1e-12):
         hp, ha, _ = host.counters()
         assert (s["proposals"], s["accepted"]) == (hp, ha), it
         assert rel(s["total_lnl"], host.total_lnl()) < 1e-11, it
+        if each is not None:
+            each(it)
     assert np.allclose(dev.taus(), host.taus(), rtol=tol, atol=0)
     assert np.allclose(dev.thetas(), host.thetas(), rtol=tol, atol=0)
     for i in range(nloci):
@@ -136,7 +139,9 @@ def test_generic_sampler_with_parameter_moves_equals_host_driver(nloci, iters, f
     the per-locus frequency / exchangeability / alpha moves (locus.c:2782-3419, prop_gamma.c:52-224) on the device —
     new values into the loci's parameter blocks, eigensystems and category rates refreshed there — against the host
     driver's param_step over libbpp_amd.so's setters: same decisions, same parameters (the category rates of a proposed
-    alpha come from device libm here and from glibc there: equal to ~1e-14, not to the bit)"""
+    alpha come from device libm here and from glibc there: not equal to the bit — +-1 ulp of libm moves a rate by 1e-14 .. 6e-14
+    relative for 0.08 <= alpha <= 5, 2e-13 .. 5e-13 for alpha <= 0.02, up to 3e-12 at alpha = 100 and 1.3e-11 at alpha = 500
+    (tests/golden/gamma_dev_sensitivity.json; the device's rates themselves: tests/test_gpu_subst_edges.py))"""
     taxa, R = 8, 4
     if fuse is not None:
         __import__("common").skip_unless_experimental(fuse)
