@@ -156,6 +156,10 @@ def lib():
         "bpa_sampler_set_subst_model": (i, [vp, u, dp, dp, d]),
         "bpa_sampler_get_subst_model": (i, [vp, u, dp, dp, dp]),
         "bpa_sampler_set_subst_moves": (None, [vp, d, d, d, d, d]),
+        "bpa_sampler_set_locus_rates": (i, [vp, dp]),
+        "bpa_sampler_get_locus_rates": (i, [vp, dp, dp]),
+        "bpa_sampler_set_locusrate_moves": (i, [vp, d, d, d, d, d, d]),
+        "bpa_sampler_locusrate_counters": (i, [vp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
         "bpa_sampler_timing": (i, [vp, dp, C.POINTER(C.c_ulong), dp, C.POINTER(C.c_ulong)]),
         "bpa_sampler_work": (i, [vp, dp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
         "bpa_sampler_kind": (i, [vp]),
@@ -203,7 +207,8 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_experimental_build", "bpa_devi
             "bpa_sampler_iterate", "bpa_sampler_get_tree", "bpa_sampler_summary",
             "bpa_sampler_enable_timing", "bpa_sampler_timing", "bpa_sampler_work", "bpa_sampler_kind", "bpa_sampler_streams", "bpa_sampler_set_p2p", "bpa_sampler_set_proposal_kernel",
             "bpa_sampler_set_program_moves", "bpa_sampler_gibbs_counters",
-            "bpa_sampler_set_subst_model", "bpa_sampler_get_subst_model", "bpa_sampler_set_subst_moves"]
+            "bpa_sampler_set_subst_model", "bpa_sampler_get_subst_model", "bpa_sampler_set_subst_moves",
+            "bpa_sampler_set_locus_rates", "bpa_sampler_get_locus_rates", "bpa_sampler_set_locusrate_moves", "bpa_sampler_locusrate_counters"]
 
 
 def _err():
@@ -711,6 +716,32 @@ class Sampler:
     def set_subst_moves(self, ft_freqs, ft_qrates, ft_alpha, alpha_a=1.0, alpha_b=1.0):
         """window widths of the per-locus frequency / exchangeability / alpha moves (0: off), gamma prior of alpha"""
         lib().bpa_sampler_set_subst_moves(self.h, ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b)
+
+    def set_locus_rates(self, mui):
+        """the loci's mutation rates mu_i (each > 0), before initialize: every branch length is (t_parent - t_child) mu_i;
+        they stay fixed unless set_locusrate_moves switches the MUI move on (the generic sampler only)"""
+        mui = _f64(mui)
+        if len(mui) != self.n:
+            raise ValueError("one rate per locus")
+        _chk(lib().bpa_sampler_set_locus_rates(self.h, _dp(mui)))
+
+    def get_locus_rates(self):
+        """(mu_i of every locus, their mean mu_bar)"""
+        mui, m = np.ones(self.n), C.c_double()
+        _chk(lib().bpa_sampler_get_locus_rates(self.h, _dp(mui), C.byref(m)))
+        return mui, m.value
+
+    def set_locusrate_moves(self, ft_mui, ft_mubar, a_mui, a_mubar=0.0, b_mubar=0.0, mubar=0.0):
+        """BPP's 'locusrate = 1 a_mubar b_mubar a_mui iid': window widths of the MUI and MUBAR moves (0: off), mu_i ~
+        gamma(a_mui, a_mui/mubar), mubar ~ gamma(a_mubar, b_mubar) (both 0: mubar is fixed); mubar > 0 sets the mean, 0 (the
+        default: changing the widths in mid-run does not reset it) keeps the current one, which starts at 1"""
+        _chk(lib().bpa_sampler_set_locusrate_moves(self.h, ft_mui, ft_mubar, a_mui, a_mubar, b_mubar, mubar))
+
+    def locusrate_counters(self):
+        """proposals and acceptances of the two rate moves (not part of summary()'s totals)"""
+        p, a = (C.c_ulong*2)(), (C.c_ulong*2)()
+        _chk(lib().bpa_sampler_locusrate_counters(self.h, p, a))
+        return dict(mui=(p[0], a[0]), mubar=(p[1], a[1]))
 
     def enable_timing(self, stride=1):
         """HIP events on every stride-th sweep / all-loci launch (0: off)"""

@@ -36,7 +36,8 @@ struct GTree                              // one per locus, in HBM
   uint32_t proposals, accepted;
   uint32_t work_nupd, work_nbr;           // node updates / fresh P-matrices / evaluations of all steps so far (bpa_sampler_work)
   uint32_t work_neval;
-  uint32_t pj_gage, pj_gage_acc, pj_gspr, pj_gspr_acc, pad_[3];    // of the proposals / accepted: the gene-node age and the prune-regraft moves (the burn-in's step-length rule wants the move types apart)
+  uint32_t pj_gage, pj_gage_acc, pj_gspr, pj_gspr_acc;    // of the proposals / accepted: the gene-node age and the prune-regraft moves (the burn-in's step-length rule wants the move types apart)
+  uint32_t pj_mui, pj_mui_acc, pad_[1];    // the locus's rate move (mode 9): counted apart, NOT part of proposals / accepted (a00_locusrate_counters)
 };
 static_assert(sizeof(GTree) % 16 == 0, "GTree is copied as uint4");
 
@@ -59,6 +60,9 @@ struct GState                             // one per lane, in LDS: what a propos
   int8_t   nin_new[MAXPOP], nc_new[MAXPOP];
 };
 
+// the mean of the loci's rates and what its move leaves (gmubar_kernel), in HBM next to the rates
+struct GLrState { double mubar, sum; unsigned long long nprop, nacc; };
+
 struct GArgs
 {
   GTree * trees, * undo;                  // [T] current (or proposed, while a step is being evaluated) / the state before the pending step
@@ -66,11 +70,17 @@ struct GArgs
   uint32_t T;
   uint32_t i0, iend;                      // the launch's loci [i0, iend) (a half-batch launch; all loci: 0, T)
   uint32_t mode;                          // 0 GAGE k, 1 GSPR k, 2 TAU, 3 MIX, 4 settle (+ THETA statistics), 5 start-up evaluation,
-                                          // 6 base frequency k, 7 exchangeability k, 8 alpha (locus.c:2782, 3168; prop_gamma.c:52)
+                                          // 6 base frequency k, 7 exchangeability k, 8 alpha (locus.c:2782, 3168; prop_gamma.c:52),
+                                          // 9 the locus's mutation rate mu_i (prop_locusrate_mui, stree.c:9225)
   uint32_t k;
   uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch),
                                           // 3 commit (start-up), 4 per-locus decisions of a substitution-parameter step
   uint32_t pend_mode, pend_k;             // pend 4: which component that step proposed
+  // per-locus mutation rates (bpa_sampler_set_locus_rates): every branch length a step writes or uses is (t_parent - t_child) mu_i
+  // (locus.c:2350).  mui == null: no rates were ever set, every mu_i is 1 and no load is made
+  double * mui, * mui_old;                // [T] the rates; [T] a pending mode-9 step's old values
+  const struct GLrState * lr;             // the rates' mean mu_bar (mode 9 reads it)
+  double ft_mui, a_mui;
   double * sm, * sm_old;                  // [T][11] freqs | exchangeabilities | alpha of every locus; [T][2] the pending step's old values
   double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
   const double * lnl_new;                 // [T] lnL of the pending step's evaluation (task = locus)
@@ -263,6 +273,16 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
       {
         const double lnl = A.lnl_new[i];
         const double lnacc = (lnl - lnl_cur) + A.hast[i];
+        if (A.pend_mode == 9)
+        {
+          // the rate move: its own counters; a rejection puts the old rate back (nothing of the parameter block moved)
+          const bool acc_ = g_accept(T.rng, A.bpp, lnacc);
+          A.trees[i].pj_mui += 1; A.trees[i].pj_mui_acc += acc_ ? 1u : 0u;
+          if (acc_) lnl_cur = lnl;
+          else { back = true; A.mui[i] = A.mui_old[i]; }
+        }
+        else
+        {
         ++nprop;
         if (g_accept(T.rng, A.bpp, lnacc)) { lnl_cur = lnl; ++nacc; }
         else
@@ -273,6 +293,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
           if (A.pend_mode == 8) m[10] = A.sm_old[2*i];
           else { double * v = A.pend_mode == 6 ? m : m + 4; const int ref = A.pend_mode == 6 ? 3 : 1; v[A.pend_k] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
           restore_par = true;
+        }
         }
       }
     }
@@ -349,11 +370,21 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
     else if (MODE >= 6)
     {
       // a substitution-parameter move (param_step of a00_driver.c): new value, then every branch, every inner node
-      double * m = A.sm + (size_t)i*11;
+      double * m = MODE == 9 ? nullptr : A.sm + (size_t)i*11;
       if (MODE == 8 && L.R < 2) ok = false;
       else
       {
-        if (MODE == 8)
+        if (MODE == 9)
+        {
+          // MUI (mui_step of a00_driver.c): sliding window on log mu_i, the gamma(a_mui, a_mui/mu_bar) prior's ratio
+          const double mu_old = A.mui[i], l_old = log(mu_old);
+          const double l_new = reflect(l_old + A.ft_mui*g_window(T.rng, A.bpp), -99.0, 99.0);
+          const double mu_new = exp(l_new);
+          A.mui_old[i] = mu_old;
+          A.mui[i] = mu_new;
+          hast = (l_new - l_old) + ((A.a_mui - 1)*log(mu_new/mu_old) - (A.a_mui/A.lr->mubar)*(mu_new - mu_old));
+        }
+        else if (MODE == 8)
         {
           const double a_old = m[10], la_old = log(a_old);
           const double la_new = reflect(la_old + A.ft_alpha*g_window(T.rng, A.bpp), -99.0, 99.0);
@@ -373,7 +404,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
           v[j] = exp(l_new); v[ref] = sum - v[j];
           hast = l_new - l_old;
         }
-        propose_par = true;
+        propose_par = MODE != 9;
         const int nn_ = 2*T.tips - 1;
         uint32_t brm = 0, ndm = 0;
         for (int k = 0; k < nn_; ++k)
@@ -444,6 +475,8 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
   }
 
   // ---- 5. the step's records for the engine's kernels
+  // (the locus's rate as it is NOW: a rate move rejected in step 1 has put the old one back, mode 9 has written the proposed one)
+  const double rate_mui = (valid && A.mui) ? A.mui[i] : 1.0;
   if (valid && MODE != 4 && A.fmt20)
   {
     const uint32_t e0 = i*A.maxmat, o0 = i*A.maxops20;
@@ -454,7 +487,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
       {
         const int x = __ffs(m) - 1;
         A.mat_task20[e0 + nm] = i; A.mat_pm20[e0 + nm] = (uint32_t)(int)T.pmat[x];
-        A.mat_length[e0 + nm] = (S.time[(int)T.parent[x]] - S.time[x])*1.0;      // rate_mui = 1 (locus.c:2350)
+        A.mat_length[e0 + nm] = (S.time[(int)T.parent[x]] - S.time[x])*rate_mui;      // locus.c:2350
       }
       for (int o = 0; o < S.nops; ++o)
       {
@@ -487,7 +520,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
       {
         const int x = __ffs(m) - 1;
         m2[nm] = MatRec2{L.slot, (uint32_t)(int)T.pmat[x]};
-        ml[nm] = (S.time[(int)T.parent[x]] - S.time[x])*1.0;                   // rate_mui = 1 (locus.c:2350)
+        ml[nm] = (S.time[(int)T.parent[x]] - S.time[x])*rate_mui;                   // locus.c:2350
       }
       for (int o = 0; o < S.nops; ++o)
       {
@@ -544,6 +577,43 @@ __global__ void __launch_bounds__(1024) gsum_decide_kernel(const double * __rest
   if (threadIdx.x) return;
   if (sum_out) sum_out[0] = sh[0];
   if (decide_on) smp::decide(sh[0], u, epoch, flag, counters, taus, sp, tau_q, -1, win_u, mix_c, mix_lnc);
+}
+
+// MUBAR (mubar_step of a00_driver.c; prop_locusrate_mubar, stree.c:9770): the sum of the loci's rates (fixed order) and the ONE
+// decision on the rates' mean — no likelihood work.  HOW = 0: the window (in (-1/2, 1/2)) and the acceptance number are the host's
+// (the uniform kernel: gs_decide's way); 1: both come from the global stream of the decisions taken on the device (GDecState::z:
+// BPP's generator, Bactrian-Laplace window, its acceptance rule) and the stream goes back there; 2: the sum only, the host decides
+// (BPA_GS_HOSTDEC) and brings the result with HOW = 3 (w: the new mean or 0 for a rejection)
+template <int HOW>
+__global__ void __launch_bounds__(1024) gmubar_kernel(const double * __restrict__ mui, uint32_t T, GLrState * lr, uint32_t * zstate,
+                                                      double ft_mubar, double a_mui, double a_mubar, double b_mubar, double w, double u)
+{
+  __shared__ double sh[1024];
+  if (HOW != 3)
+  {
+    double acc = 0;
+    for (uint32_t i = threadIdx.x; i < T; i += 1024) acc += mui[i];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t h = 512; h > 0; h >>= 1)
+    {
+      if (threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x) return;
+  if (HOW == 2) { lr->sum = sh[0]; return; }
+  if (HOW == 3) { lr->nprop += 1; if (w > 0) { lr->nacc += 1; lr->mubar = w; } return; }
+  lr->sum = sh[0];
+  const double m_old = lr->mubar, l_old = log(m_old);
+  smp2::Stream<true> g{(a00_rng_t)(HOW == 1 ? *zstate : 0u)};
+  const double l_new = reflect(l_old + ft_mubar*(HOW == 1 ? g.window() : w), -99.0, 99.0);
+  const double m_new = exp(l_new), b_new = a_mui/m_new, b_old = a_mui/m_old;
+  const double lnacc = A00_MUBAR_LNACC(l_old, l_new, m_old, m_new, b_old, b_new, a_mui, a_mubar, b_mubar, (double)T, sh[0]);
+  const bool acc_ = HOW == 1 ? g.accept(lnacc) : (lnacc >= 0 || u < exp(lnacc));
+  if (HOW == 1) *zstate = (uint32_t)g.r;
+  lr->nprop += 1;
+  if (acc_) { lr->nacc += 1; lr->mubar = m_new; }
 }
 
 // ---- the program's THETA / TAU / MIX for the generic samplers: the loci's sums on the device, the decision on the host ----

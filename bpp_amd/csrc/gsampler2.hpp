@@ -92,6 +92,11 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
   const double d_tau_w = (MODE == 2 && A.dstep) ? A.dstep->tau_w : A.tau_w;
   const double d_mix_c = (MODE == 3 && A.dstep) ? A.dstep->mix_c : A.mix_c, d_mix_lnc = (MODE == 3 && A.dstep) ? A.dstep->mix_lnc : A.mix_lnc;
   const double d_lnl = A.lnl_new[ic], d_logpr = A.logpr_new[ic], d_hast = A.hast[ic];
+  // the locus's mutation rate (null: none was ever set, 1 without a load) and, when the step being settled moved it, the old
+  // one: which of the two scales this step's branch lengths is known after the settle phase
+  const double mui_r = A.mui ? A.mui[ic] : 1.0;
+  const double mui_o = (A.mui && C.pend == 4 && A.pend_mode == 9) ? A.mui_old[ic] : mui_r;
+  double rate_mui = mui_r;
 
   if (lane < (uint32_t)(3*MAXPOP)) s_tau[lane] = tau_r;
   if (lane < 16u) s_anc[lane] = lane < (uint32_t)MAXPOP ? (uint32_t)SP.anc[lane] : 0u;
@@ -159,6 +164,16 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
       if (d_active)
       {
         const double lnacc = (d_lnl - lnl_cur) + d_hast;
+        if (A.pend_mode == 9)
+        {
+          // the rate move (gstep_kernel's step 1): its own counters, a rejection puts the old rate back
+          const bool acc_ = rng.accept(lnacc);
+          if (li == 0) { A.trees[i].pj_mui += 1; A.trees[i].pj_mui_acc += acc_ ? 1u : 0u; }
+          if (acc_) lnl_cur = d_lnl;
+          else { back = true; rate_mui = mui_o; if (li == 0) A.mui[i] = mui_o; }
+        }
+        else
+        {
         ++nprop;
         if (rng.accept(lnacc)) { lnl_cur = d_lnl; ++nacc; }
         else
@@ -171,6 +186,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
             else { double * v = A.pend_mode == 6 ? m : m + 4; const int ref = A.pend_mode == 6 ? 3 : 1; v[A.pend_k] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
           }
           restore_par = true;
+        }
         }
       }
     }
@@ -396,7 +412,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
     {
       const int x = nth_bit(brm, li);
       A.mat_task20[e0 + li] = i; A.mat_pm20[e0 + li] = (uint32_t)T.pidx(x);
-      A.mat_length[e0 + li] = (S.time[(int)T.parent[x]] - S.time[x])*1.0;                 // rate_mui = 1 (locus.c:2350)
+      A.mat_length[e0 + li] = (S.time[(int)T.parent[x]] - S.time[x])*rate_mui;            // locus.c:2350
     }
     else if ((uint32_t)li < A.maxmat) A.mat_task20[e0 + li] = 0xffffffffu;
 #pragma unroll
@@ -429,7 +445,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
     {
       const int x = nth_bit(brm, li);
       m2[li] = MatRec2{L.slot, (uint32_t)T.pidx(x)};
-      ml[li] = (S.time[(int)T.parent[x]] - S.time[x])*1.0;                                // rate_mui = 1 (locus.c:2350)
+      ml[li] = (S.time[(int)T.parent[x]] - S.time[x])*rate_mui;                           // locus.c:2350
     }
     else if ((uint32_t)li < A.maxmat) m2[li] = MatRec2{0xffffffffu, 0u};                    // entries of the last step this one does not use
     if (A.fuse_pm)
@@ -446,7 +462,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
         const uint32_t j = q/R, k = q - j*R;
         const int x = nth_bit(brm, (int)j);
         double * dst = pf_pmat + (size_t)T.pidx(x)*R*pf_pstride;
-        const double t = (S.time[(int)T.parent[x]] - S.time[x])*1.0;
+        const double t = (S.time[(int)T.parent[x]] - S.time[x])*rate_mui;
         const double rate = k == k0 ? pf_rate : L.par[par_rates(R) + k];
         const uint32_t mi = pf_model == 0 ? 0u : k == k0 ? pf_mi : (uint32_t)L.par[par_param_idx(R) + k];
         double pmv[PMB];                                        // (constant indices below: registers)

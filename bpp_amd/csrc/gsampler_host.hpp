@@ -33,6 +33,22 @@ static int gs_subst_ready(bpa_sampler * s)
   return 1;
 }
 
+// the per-locus rates' device arrays (rates, a pending step's old values, their mean): made when rates were set or a
+// locus-rate move is on — a sampler that never heard of rates passes null pointers, which its kernels read as "every rate 1"
+static bool gs_lr_moves(const bpa_sampler * s) { return s->g_lr_ft[0] > 0 || s->g_lr_ft[1] > 0; }
+static int gs_lr_ready(bpa_sampler * s)
+{
+  if (s->g_mui.p || (s->g_mui_host.empty() && !gs_lr_moves(s))) return 1;
+  const unsigned T = s->nloci;
+  if (s->g_mui_host.size() != T) s->g_mui_host.assign(T, 1.0);
+  if (!upload(s->g_mui, s->g_mui_host.data(), T) || !upload(s->g_mui_old, s->g_mui_host.data(), T) || !upload(s->g_lr, &s->g_lr_host, 1)) return 0;
+  return 1;
+}
+static void gs_lr_args(const bpa_sampler * s, gsm::GArgs & a)
+{
+  a.mui = s->g_mui.p; a.mui_old = s->g_mui_old.p; a.lr = s->g_lr.p; a.ft_mui = s->g_lr_ft[0]; a.a_mui = s->g_a_mui;
+}
+
 // K6 for every locus of the sampler from the values now in its parameter block (pll_update_eigen, locus.c:2462-2476)
 static int gs_refresh_eigen(bpa_sampler * s)
 {
@@ -175,6 +191,8 @@ static int gs_upload(bpa_sampler * s)
     return 0;
   s->g_sm.free();                                    // (re-made from the host copy by gs_subst_ready when a move is on)
   if (!gs_subst_ready(s)) return 0;
+  s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free();
+  if (!gs_lr_ready(s)) return 0;
   // every slot starts as "not part of the step", every matrix entry as a hole
   HIPCHK(hipMemsetAsync(s->g_recs.p, 0xff, nrec*sizeof(uint4), e->stream));
   HIPCHK(hipMemsetAsync(s->g_mat2.p, 0xff, nmat*sizeof(MatRec2), e->stream));
@@ -309,6 +327,8 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   a.ft_freqs = s->g_ft[0]; a.ft_qrates = s->g_ft[1]; a.ft_alpha = s->g_ft[2]; a.alpha_a = s->g_alpha_a; a.alpha_b = s->g_alpha_b;
   a.bpp = s->kernel_bpp ? 1u : 0u; a.prog = gs_prog(s) ? 1u : 0u; a.t2h3 = s->g_t2h3.p; a.tau_w = tau_w;
   a.slot_tab = e->d_slot_tab.p;
+  gs_lr_args(s, a);
+  if (mode == 9 && !a.mui) return fail("bpa_sampler: a rate step without the rates' arrays");
   a.dstep = (s->gp_dev && (mode == 2 || mode == 3)) ? s->g_dst.p : nullptr;
   // a frequency / exchangeability step — proposed now, or rolled back now for the loci that rejected it — leaves
   // parameter blocks whose eigensystems are stale: refreshed before the next evaluation (gs_eval)
@@ -334,9 +354,10 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   static const bool gs_v1 = BPA_EXP_SWITCH("BPA_GS_V1") != nullptr;
   // the step's P-matrices by the proposal's lane groups (gstep2_body) instead of a launch of their own: 4-state loci on the
   // packing whose step launch does not make them itself (gs_fuse_a), no substitution-parameter step pending or rolled back
-  // since the eigensystems were last refreshed (BPA_GS_FUSEPM=0: the dense launch)
+  // since the eigensystems were last refreshed (BPA_GS_FUSEPM=0: the dense launch).  A pending RATE step (mode 9) does not turn
+  // this off: it wrote no parameter block, and the lane group reads the locus's rate after it has settled that step
   s->g_pm_fused = false;
-  if (mode <= 3 && !gs_v1 && !gs_diff && !s->g_s20 && !s->g_alljc && e->usedata && s->g_pend != 4 && !s->g_eigen_dirty && !gs_fuse_a(s))
+  if (mode <= 3 && !gs_v1 && !gs_diff && !s->g_s20 && !s->g_alljc && e->usedata && (s->g_pend != 4 || s->g_pend_mode == 9) && !s->g_eigen_dirty && !gs_fuse_a(s))
   {
     s->g_pm_fused = s->env_fusepm;
   }
@@ -458,7 +479,7 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
     {
 #define GS_CASE(M_) case M_: if (s->maxtips <= 8) hipLaunchKernelGGL((gsm::gstep_kernel<M_, 8>), grid, block, 0, st, a); \
                             else                 hipLaunchKernelGGL((gsm::gstep_kernel<M_, 16>), grid, block, 0, st, a); break
-      GS_CASE(0); GS_CASE(1); GS_CASE(2); GS_CASE(3); GS_CASE(4); GS_CASE(5); GS_CASE(6); GS_CASE(7); GS_CASE(8);
+      GS_CASE(0); GS_CASE(1); GS_CASE(2); GS_CASE(3); GS_CASE(4); GS_CASE(5); GS_CASE(6); GS_CASE(7); GS_CASE(8); GS_CASE(9);
 #undef GS_CASE
       default: return fail("bpa_sampler: unknown step mode");
     }
@@ -695,6 +716,7 @@ static int gs_chain(bpa_sampler * s)
   a.sp = s->sp;
   a.pend_mode = s->g_pend_mode; a.pend_k = s->g_pend_k; a.sm = s->g_sm.p; a.sm_old = s->g_sm_old.p;
   a.bpp = s->kernel_bpp ? 1u : 0u; a.prog = gs_prog(s) ? 1u : 0u; a.t2h3 = s->g_t2h3.p;
+  gs_lr_args(s, a);
   a.fmt20 = 1u; a.maxops20 = s->g_maxops;
   a.ops20 = s->g_ops20.p; a.op_rng20 = s->g_oprng.p; a.root20 = s->g_root20.p; a.mat_task20 = s->g_mtask.p; a.mat_pm20 = s->g_mpm.p;
   a.i0 = 0; a.iend = s->nloci;
@@ -1146,10 +1168,50 @@ static int gs_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
   return mix ? gs_dec_launch<2>(s, -1, -1) : gs_dec_launch<1>(s, q, q + 1);
 }
 
+// MUBAR: the pending rate step is settled first (a launch of its own: the sum must see the rates the loci kept), then ONE
+// launch sums and decides — with the host's two numbers (our own kernel), from the device's global stream (the program's moves
+// decided on the device: the two draws sit between MIX's acceptance number and the next iteration's first window, where
+// a00_iterate puts them) — or, BPA_GS_HOSTDEC=1, the host fetches the sum and decides, as that form does for TAU and MIX
+static int gs_mubar(bpa_sampler * s)
+{
+  bpa_engine * e = s->eng;
+  if (!gs_step(s, 4)) return 0;
+  const double ft = s->g_lr_ft[1], am = s->g_a_mui, a = s->g_a_mubar, b = s->g_b_mubar;
+  if (!s->kernel_bpp)
+  {
+    const double w = a00_rndu(&s->grng) - 0.5, u = a00_rndu(&s->grng);
+    hipLaunchKernelGGL((gsm::gmubar_kernel<0>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, w, u);
+  }
+  else if (s->gp_dev)
+    hipLaunchKernelGGL((gsm::gmubar_kernel<1>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, &s->g_dst.p->z, ft, am, a, b, 0.0, 0.0);
+  else
+  {
+    hipLaunchKernelGGL((gsm::gmubar_kernel<2>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, 0.0, 0.0);
+    HIPCHK(hipGetLastError());
+    s->launches++;
+    gsm::GLrState st;
+    HIPCHK(hipMemcpyAsync(&st, s->g_lr.p, sizeof st, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    unsigned int gz = (unsigned int)s->grng;
+    const double l_old = std::log(st.mubar), l_new = a00_reflect(l_old + ft*a00_bpp_rnd_symmetrical(&gz), -99.0, 99.0);
+    const double m_new = std::exp(l_new);
+    const double lnacc = A00_MUBAR_LNACC(l_old, l_new, st.mubar, m_new, am/st.mubar, am/m_new, am, a, b, (double)s->nloci, st.sum);
+    const bool acc = lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc);
+    gs_declog("mubar", 0, lnacc, acc);
+    s->grng = (a00_rng_t)gz;
+    hipLaunchKernelGGL((gsm::gmubar_kernel<3>), dim3(1), dim3(1), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, acc ? m_new : 0.0, 0.0);
+  }
+  HIPCHK(hipGetLastError());
+  s->launches++;
+  return 1;
+}
+
 static int gs_iterate(bpa_sampler * s, unsigned iterations)
 {
   bpa_engine * e = s->eng;
   if (!gs_subst_ready(s)) return 0;
+  if (gs_lr_moves(s) && !(s->g_a_mui > 0)) return fail("bpa_sampler: the locus-rate moves need a_mui > 0");
+  if (!gs_lr_ready(s)) return 0;
   s->host_current = false;
   const bool prog = gs_prog(s);
   if (s->kernel_bpp && !prog) return fail("bpa_sampler: on a generic sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
@@ -1237,6 +1299,9 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
     if (s->g_ft[2] > 0)                                   { if (!gs_step(s, 8, 0) || !gs_eval(s, 0)) return 0; }
     if (s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0)
       for (bpa_locus * l : s->loci) l->host_par_stale = true;            // the device blocks moved ahead of the host mirrors
+    // ... then the loci's rates and their mean (method.c:5745-5773; mui_step / mubar_step of a00_driver.c)
+    if (s->g_lr_ft[0] > 0) { if (!gs_step(s, 9) || !gs_eval(s, 0)) return 0; }
+    if (s->g_lr_ft[1] > 0 && (s->g_a_mubar > 0 || s->g_b_mubar > 0)) { if (!gs_mubar(s)) return 0; }
   }
   return gs_join(s);                 // whoever uses the engine's stream next sees both halves
 }
@@ -1267,6 +1332,11 @@ static int gs_download(bpa_sampler * s)
   HIPCHK(hipMemcpyAsync(s->g_trees.data(), s->g_dev.p, s->nloci*sizeof(gsm::GTree), hipMemcpyDeviceToHost, e->stream));
   if (s->g_sm.p && !s->g_sm_host.empty())
     HIPCHK(hipMemcpyAsync(s->g_sm_host.data(), s->g_sm.p, s->g_sm_host.size()*sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  if (s->g_mui.p)
+  {
+    HIPCHK(hipMemcpyAsync(s->g_mui_host.data(), s->g_mui.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&s->g_lr_host, s->g_lr.p, sizeof(gsm::GLrState), hipMemcpyDeviceToHost, e->stream));
+  }
   HIPCHK(hipStreamSynchronize(e->stream));
   return 1;
 }
@@ -1305,4 +1375,71 @@ extern "C" void bpa_sampler_set_subst_moves(bpa_sampler_t * s, double ft_freqs, 
   if (s->comp) { (void)comp_each(s, [&](bpa_sampler * p) { if (p->generic) bpa_sampler_set_subst_moves(p, ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b); return 1; }); return; }
   // (nothing to upload: the widths travel with every launch, the moves' tables are made when first needed — gs_subst_ready)
   s->g_ft[0] = ft_freqs; s->g_ft[1] = ft_qrates; s->g_ft[2] = ft_alpha; s->g_alpha_a = alpha_a; s->g_alpha_b = alpha_b;
+}
+
+// ---- per-locus mutation rates (include/bpp_amd.h): the generic sampler's; every other kind refuses them
+static int lr_refuse(const bpa_sampler * s, const char * who)
+{
+  const char * kind = s->comp ? "composite" : s->big ? "big-tree" : "persistent / sweep";
+  if (!s->comp && s->generic) return 1;
+  static thread_local std::string msg;
+  msg = std::string(who) + ": per-locus rates and their moves run on the generic sampler only (this one is the " + kind +
+        " sampler); BPA_SMP_GENERIC=1 makes the generic sampler take loci the LDS kernels would otherwise";
+  return fail(msg.c_str());
+}
+
+extern "C" int bpa_sampler_set_locus_rates(bpa_sampler_t * s, const double * mui)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!lr_refuse(s, "bpa_sampler_set_locus_rates")) return 0;
+  if (!mui) return fail("bpa_sampler_set_locus_rates: null argument");
+  for (unsigned i = 0; i < s->nloci; ++i)
+    if (!(mui[i] > 0) || !std::isfinite(mui[i])) return fail("bpa_sampler_set_locus_rates: every rate is > 0 and finite");
+  if (s->uploaded)
+    return fail("bpa_sampler_set_locus_rates: the sampler is running — set the loci's starting rates before bpa_sampler_initialize");
+  s->g_mui_host.assign(mui, mui + s->nloci);
+  return 1;
+}
+
+extern "C" int bpa_sampler_get_locus_rates(bpa_sampler_t * s, double * mui, double * mubar)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!lr_refuse(s, "bpa_sampler_get_locus_rates")) return 0;
+  if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
+  if (mui) for (unsigned i = 0; i < s->nloci; ++i) mui[i] = s->g_mui_host.size() == s->nloci ? s->g_mui_host[i] : 1.0;
+  if (mubar) *mubar = s->g_lr_host.mubar;
+  return 1;
+}
+
+extern "C" int bpa_sampler_set_locusrate_moves(bpa_sampler_t * s, double ft_mui, double ft_mubar, double a_mui, double a_mubar, double b_mubar, double mubar)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  const bool on = ft_mui > 0 || ft_mubar > 0;
+  if ((s->comp || !s->generic) && !on && ft_mui == 0 && ft_mubar == 0) return 1;        // (nothing asked for)
+  if (!lr_refuse(s, "bpa_sampler_set_locusrate_moves")) return 0;
+  if (!(ft_mui >= 0) || !(ft_mubar >= 0) || !(a_mubar >= 0) || !(b_mubar >= 0) || !(mubar >= 0) || !std::isfinite(mubar))
+    return fail("bpa_sampler_set_locusrate_moves: widths, prior parameters and mubar are >= 0 and finite");
+  if (on && !(a_mui > 0)) return fail("bpa_sampler_set_locusrate_moves: a_mui > 0 while a move is on");
+  // (the widths and the priors' parameters travel with every launch; a new mean goes to the device next to the rates)
+  if (mubar > 0)
+  {
+    // (the host copy is brought level first: iterations since the last download have moved the mean and its counters)
+    if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
+    s->g_lr_host.mubar = mubar;
+    if (s->uploaded && s->g_lr.p) HIPCHK(hipMemcpy(s->g_lr.p, &s->g_lr_host, sizeof(gsm::GLrState), hipMemcpyHostToDevice));
+  }
+  s->g_lr_ft[0] = ft_mui; s->g_lr_ft[1] = ft_mubar; s->g_a_mui = a_mui; s->g_a_mubar = a_mubar; s->g_b_mubar = b_mubar;
+  return 1;
+}
+
+extern "C" int bpa_sampler_locusrate_counters(bpa_sampler_t * s, unsigned long prop[2], unsigned long acc[2])
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!lr_refuse(s, "bpa_sampler_locusrate_counters")) return 0;
+  if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
+  unsigned long p = 0, a = 0;
+  for (const auto & t : s->g_trees) { p += t.pj_mui; a += t.pj_mui_acc; }
+  if (prop) { prop[0] = p; prop[1] = (unsigned long)s->g_lr_host.nprop; }
+  if (acc) { acc[0] = a; acc[1] = (unsigned long)s->g_lr_host.nacc; }
+  return 1;
 }

@@ -68,6 +68,11 @@ struct a00_driver
   double * sm; int * sm_ncat; a00_param_fn setpar;
   double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
   double * sm_old;                      /* proposed component's old values per slot: [2] for freqs / qrates, alpha */
+  /* per-locus mutation rates (a00_set_locus_rates / a00_set_locusrate_moves): the rates themselves are the trees' rate_mui */
+  double * mui, * mui_old;              /* what a00_set_locus_rates left (a tree set afterwards starts from it); a pending MUI step's old values */
+  double ft_mui, ft_mubar, a_mui, a_mubar, b_mubar, mubar;
+  unsigned long lr_prop[2], lr_acc[2];  /* 0: MUI, 1: MUBAR — apart from proposals / accepted */
+  int initialized;
   /* per-locus staging of a step (a00_set_threads): the loci of a step are proposed in parallel — every draw of a
      per-locus proposal comes from that locus's own stream, so the trajectory does not depend on the thread count —
      each into its own row; `compact` then lines the rows up as the step's slots in locus order */
@@ -196,6 +201,7 @@ a00_driver_t * a00_create(unsigned nloci, a00_eval_fn eval, void * ctx, unsigned
   d->c_lo = 0; d->c_hi = nloci;
   d->ft_gage = 0.004; d->ft_gspr = 0.004; d->ft_tau = 0.001; d->ft_mix = 0.3;
   d->threads = 1;
+  d->mubar = 1.0;
   d->theta_slide_prob = 0.1;
   { const char * ev = getenv("A00_THREADS"); if (ev && atoi(ev) > 0) a00_set_threads(d, atoi(ev)); }
   d->w_nb = (int *)calloc(nloci, sizeof(int)); d->w_nn = (int *)calloc(nloci, sizeof(int));
@@ -220,7 +226,7 @@ void a00_destroy(a00_driver_t * d)
   }
   d->view[d->cur_view].s_br = d->s_br; d->view[d->cur_view].s_nd = d->s_nd;
   { int v; for (v = 0; v < 3; ++v) { free(d->view[v].s_br); free(d->view[v].s_nd); } }
-  free(d->rng); free(d->zrng); free(d->sm); free(d->sm_ncat); free(d->sm_old); free(d->trees); free(d->b_locus); free(d->b_tree); free(d->b_br_off); free(d->b_nd_off);
+  free(d->rng); free(d->zrng); free(d->sm); free(d->sm_ncat); free(d->sm_old); free(d->mui); free(d->mui_old); free(d->trees); free(d->b_locus); free(d->b_tree); free(d->b_br_off); free(d->b_nd_off);
   free(d->t_br_off); free(d->t_nd_off);
   free(d->b_logpr); free(d->p_logpr); free(d->p_delta); free(d->p_slot); free(d->u_pop);
   free(d->w_br); free(d->w_nd); free(d->w_nb); free(d->w_nn); free(d->w_hast); free(d->w_logpr); free(d->w_diff);
@@ -234,7 +240,7 @@ int a00_set_tree(a00_driver_t * d, unsigned i, int tips, const int * left, const
   a00_tree_t * t = d->trees + i;
   const int n = 2*tips - 1; int k;
   if (i >= d->nloci || n > MAXN || tips < 2) return 0;
-  t->tips = tips; t->n = n; t->root = root; t->rate_mui = 1.0; t->lnl = 0;
+  t->tips = tips; t->n = n; t->root = root; t->rate_mui = d->mui ? d->mui[i] : 1.0; t->lnl = 0;
   /* one block per locus — time | left | right | parent | clv | pmat | scaler | pop — and one of the same shape for the
      roll-back copy: a snapshot is ONE memcpy of 36 n bytes (was eight of separately allocated arrays) */
   {
@@ -539,6 +545,7 @@ int a00_initialize(a00_driver_t * d)
   }
   if (compact(d) != d->nloci || !step_eval(d, d->nloci)) return 0;
   for (i = 0; i < d->nloci; ++i) d->trees[i].lnl = d->s_lnl[i];
+  d->initialized = 1;
   return 1;
 }
 
@@ -1232,6 +1239,93 @@ static int param_step(a00_driver_t * d, int which, int j)
   return 1;
 }
 
+/* ---- per-locus mutation rates (bpp_amd_host.h): mu_i of the conditional-iid prior under the strict clock */
+int a00_set_locus_rates(a00_driver_t * d, const double * mui)
+{
+  unsigned i;
+  if (!mui || d->initialized) return 0;                   /* (the start-up evaluation has used the rates) */
+  for (i = 0; i < d->nloci; ++i) if (!(mui[i] > 0) || !(mui[i] < INFINITY)) return 0;
+  if (!d->mui) d->mui = (double *)calloc(d->nloci, sizeof(double));
+  if (!d->mui) return 0;
+  for (i = 0; i < d->nloci; ++i) { d->mui[i] = mui[i]; if (d->trees[i].time) d->trees[i].rate_mui = mui[i]; }
+  return 1;
+}
+void a00_get_locus_rates(const a00_driver_t * d, double * mui, double * mubar)
+{
+  unsigned i;
+  if (mui) for (i = 0; i < d->nloci; ++i) mui[i] = d->trees[i].time ? d->trees[i].rate_mui : d->mui ? d->mui[i] : 1.0;
+  if (mubar) *mubar = d->mubar;
+}
+int a00_set_locusrate_moves(a00_driver_t * d, double ft_mui, double ft_mubar, double a_mui, double a_mubar, double b_mubar, double mubar)
+{
+  if (!(ft_mui >= 0) || !(ft_mubar >= 0) || !(a_mubar >= 0) || !(b_mubar >= 0) || !(mubar >= 0) || !(mubar < INFINITY)) return 0;
+  if ((ft_mui > 0 || ft_mubar > 0) && !(a_mui > 0)) return 0;
+  d->ft_mui = ft_mui; d->ft_mubar = ft_mubar; d->a_mui = a_mui; d->a_mubar = a_mubar; d->b_mubar = b_mubar;
+  if (mubar > 0) d->mubar = mubar;
+  return 1;
+}
+void a00_locusrate_counters(const a00_driver_t * d, unsigned long prop[2], unsigned long acc[2])
+{
+  if (prop) { prop[0] = d->lr_prop[0]; prop[1] = d->lr_prop[1]; }
+  if (acc) { acc[0] = d->lr_acc[0]; acc[1] = d->lr_acc[1]; }
+}
+
+/* MUI: the rate of every locus (prop_locusrate_mui, stree.c:9225, the hierarchical prior under the strict clock): sliding
+   window on log mu_i, every branch's P-matrix from (t_parent - t_child) mu_i', every inner node again; the MSC density stays */
+static int mui_step(a00_driver_t * d)
+{
+  unsigned i, s;
+  if (!staging_ready(d)) return 0;
+  if (!d->mui_old && !(d->mui_old = (double *)calloc(d->nloci, sizeof(double)))) return 0;
+  for (i = 0; i < d->nloci; ++i)
+  {
+    a00_tree_t * t = d->trees + i;
+    int br[MAXN], nd[MAXN], nb = 0, nn = 0, k;
+    const double mu_old = t->rate_mui, l_old = log(mu_old);
+    const double l_new = a00_reflect(l_old + d->ft_mui*draw_window(d, (long)i), -99.0, 99.0);
+    const double mu_new = exp(l_new);
+    const double hast = (l_new - l_old) + ((d->a_mui - 1)*log(mu_new/mu_old) - (d->a_mui/d->mubar)*(mu_new - mu_old));      /* stree.c:9293, 9309 */
+    d->mui_old[i] = mu_old;
+    t->rate_mui = mu_new;
+    snapshot(d, i);
+    for (k = 0; k < t->n; ++k)
+    {
+      if (t->left[k] >= 0) nd[nn++] = k;
+      if (t->parent[k] >= 0) br[nb++] = k;
+    }
+    install_local(d, i, br, nb, nd, nn, hast, t->logpr);
+  }
+  if (compact(d) != d->nloci || !step_eval(d, d->nloci)) return 0;
+  for (s = 0; s < d->nloci; ++s)
+  {
+    const unsigned li = d->s_locus[s]; a00_tree_t * t = d->trees + li;
+    const double lnacc = (d->s_lnl[s] - t->lnl) + d->s_hast[s];
+    d->lr_prop[0]++;
+    if (accept(d, (long)li, lnacc, -1.0)) { t->lnl = d->s_lnl[s]; d->lr_acc[0]++; continue; }
+    restore(d, li);
+    t->rate_mui = d->mui_old[li];
+  }
+  return 1;
+}
+
+/* MUBAR: the mean of the rates' gamma(a_mui, a_mui/mubar) (prop_locusrate_mubar, stree.c:9770): sliding window on log mubar,
+   gamma(a_mubar, b_mubar) prior, ONE decision from the sum of the rates; no likelihood work */
+static int mubar_step(a00_driver_t * d)
+{
+  unsigned i; double sum = 0, lnacc; int acc_;
+  const double old = d->mubar, l_old = log(old);
+  const double l_new = a00_reflect(l_old + d->ft_mubar*draw_window(d, -1), -99.0, 99.0);
+  const double uacc = d->kernel == A00_KERNEL_BPP ? -1.0 : draw_u(d, -1);
+  const double mnew = exp(l_new), bnew = d->a_mui/mnew, bold = d->a_mui/old;
+  for (i = 0; i < d->nloci; ++i) sum += d->trees[i].rate_mui;
+  lnacc = A00_MUBAR_LNACC(l_old, l_new, old, mnew, bold, bnew, d->a_mui, d->a_mubar, d->b_mubar, (double)d->nloci, sum);
+  d->lr_prop[1]++;
+  acc_ = accept(d, -1, lnacc, uacc);
+  declog("mubar", 0, lnacc, uacc, acc_);
+  if (acc_) { d->lr_acc[1]++; d->mubar = mnew; }
+  return 1;
+}
+
 int a00_iterate(a00_driver_t * d)
 {
   unsigned i; int k, maxtips = 0;
@@ -1257,6 +1351,9 @@ int a00_iterate(a00_driver_t * d)
     if (d->ft_qrates > 0) for (k = 0; k < 6; ++k) if (k != 1 && !param_step(d, 2, k)) return 0;
     if (d->ft_alpha > 0 && !param_step(d, 4, 0)) return 0;
   }
+  /* ... then the loci's rates and their mean (method.c:5745-5773); a fixed mean (a_mubar = b_mubar = 0) draws nothing */
+  if (d->ft_mui > 0 && !mui_step(d)) return 0;
+  if (d->ft_mubar > 0 && (d->a_mubar > 0 || d->b_mubar > 0) && !mubar_step(d)) return 0;
   return 1;
 }
 

@@ -1187,6 +1187,14 @@ struct bpa_sampler
   DevBuf<uint32_t> g_ids;
   double g_ft[3] = {0, 0, 0}, g_alpha_a = 1, g_alpha_b = 1;
   unsigned g_pend_mode = 0, g_pend_k = 0;
+  // per-locus mutation rates (bpa_sampler_set_locus_rates / bpa_sampler_set_locusrate_moves): the rates and a pending rate
+  // step's old values in arrays of their own ([T] doubles; never made when no rate is set and no move is on), their mean and
+  // the MUBAR counters next to them; host copies, level with the device after a download
+  std::vector<double> g_mui_host;
+  gsm::GLrState g_lr_host{1.0, 0.0, 0ull, 0ull};
+  DevBuf<double> g_mui, g_mui_old;
+  DevBuf<gsm::GLrState> g_lr;
+  double g_lr_ft[2] = {0, 0}, g_a_mui = 0, g_a_mubar = 0, g_b_mubar = 0;
   bool g_eigen_dirty = false;
   bool g_level_eval = false;            // gs_level_roots: this evaluation stores every parent
   bool g_root_stale = false;            // a step's evaluation left the root's CLV unstored (flags bit 11): gs_download brings the buffers level
@@ -1382,6 +1390,7 @@ extern "C" void bpa_sampler_destroy(bpa_sampler_t * s)
   s->g_dev.free(); s->g_undo.free(); s->g_loc.free(); s->g_lnl.free(); s->g_lnlcur.free(); s->g_hast.free(); s->g_logpr.free(); s->g_delta.free(); s->g_site.free();
   s->g_len.free(); s->g_lograt.free(); s->g_active.free(); s->g_recs.free(); s->g_mat2.free(); s->g_bmo.free();
   s->g_sm.free(); s->g_sm_old.free(); s->g_ids.free();
+  s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free();
   s->b_dev.free(); s->b_undo.free(); s->b_thr.free();
   s->g_ops20.free(); s->g_oprng.free(); s->g_root20.free(); s->g_mtask.free(); s->g_mpm.free(); s->g_tlocus.free(); s->g_tpat.free(); s->g_ttask.free(); s->g_tn0.free(); s->g_rscaler.free();
   s->v2_wave_off.free(); s->v2_loc.free(); s->v2_pat.free(); s->v2_xbuf.free(); s->v2_grng.free(); s->v2_err.free(); s->v2_prof.free(); s->v2_declog.free(); s->v2_sp.free();
@@ -2211,6 +2220,9 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
   bpa_engine * e = s->eng;
   std::lock_guard<std::recursive_mutex> lock_(e->mtx);
   if (s->comp) return comp_run(s, 1, iterations);
+  // the locus-rate moves decide from the sum of ONE rank's rates: refused with several ranks, before anything is launched
+  if (s->generic && (s->g_lr_ft[0] > 0 || s->g_lr_ft[1] > 0) && (s->allreduce || s->p2p))
+    return fail("bpa_sampler_iterate: the locus-rate moves run on one rank (an all-reduce callback or the mailboxes are installed: the sum of the rates over the ranks is not exchanged)");
   if (!sampler_upload(s)) return 0;
   s->host_current = false;
   if (s->big) return gb_iterate(s, iterations);

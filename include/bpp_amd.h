@@ -424,6 +424,30 @@ int  bpa_sampler_summary(bpa_sampler_t *, double * total_lnl, unsigned long * pr
 int  bpa_sampler_set_subst_model(bpa_sampler_t *, unsigned i, const double * freqs /* 4 */, const double * qrates /* 6 */, double alpha);
 int  bpa_sampler_get_subst_model(bpa_sampler_t *, unsigned i, double * freqs, double * qrates, double * alpha);
 void bpa_sampler_set_subst_moves(bpa_sampler_t *, double ft_freqs, double ft_qrates, double ft_alpha, double alpha_a, double alpha_b);
+/* Per-locus mutation rates: BPP's 'locusrate = 1 a_mubar b_mubar a_mui iid' under the strict clock — mu_i ~ gamma(a_mui,
+   a_mui/mubar) per locus around a mean mubar ~ gamma(a_mubar, b_mubar) (the conditional-iid, "hierarchical" prior).  Every
+   branch length the sampler writes or uses is (t_parent - t_child) mu_i (locus.c:2350); the MSC density does not see the
+   rates.  The two moves run after the substitution-parameter moves, as in cmd_run (method.c:5745-5773):
+     MUI    prop_locusrate_mui, stree.c:9225: per locus a sliding window on log mu_i (reflected into (-99, 99)), window and
+            acceptance number from the locus's own stream; lnacc = delta log mu_i + (a_mui - 1) log(mu_i'/mu_i)
+            - (a_mui/mubar)(mu_i' - mu_i) + delta lnL; every P-matrix and every partial of the locus again, all on the device
+            (step mode 9 of the generic sampler);
+     MUBAR  prop_locusrate_mubar, stree.c:9770: ONE decision for all loci from the sum of the rates (summed and decided on
+            the device), window then acceptance number from the global stream; no likelihood work.  a_mubar = b_mubar = 0:
+            mubar is fixed (cfile.c:2903; the program then uses 1) — the step does not run and draws nothing.
+   Meanings as the host driver's a00_set_locus_rates / a00_get_locus_rates / a00_set_locusrate_moves /
+   a00_locusrate_counters (bpp_amd_host.h): rates [nloci], each > 0 and finite, before bpa_sampler_initialize (ft_mui = 0 keeps
+   them fixed: the program's rates from a file); widths 0 = that move is off (default: both off), changeable at any time;
+   mubar > 0 sets the mean, 0 keeps the current one; counters: index 0 = MUI, 1 = MUBAR, apart from bpa_sampler_summary's
+   totals.  A sampler on which none of this is called computes what it always did, to the bit.
+   The generic sampler only (BPA_SAMPLER_GENERIC; BPA_SMP_GENERIC=1 makes it take loci the LDS kernels would otherwise):
+   rates or a non-zero width on any other kind fail, as do a rate <= 0 or not finite, a_mui <= 0 while a move is on, rates
+   after bpa_sampler_initialize, and — when bpa_sampler_iterate is called — the moves together with an all-reduce callback
+   (one rank only).  Each returns 1, or 0 with bpa_last_error set.                                                        */
+int  bpa_sampler_set_locus_rates(bpa_sampler_t *, const double * mui /* [nloci] */);
+int  bpa_sampler_get_locus_rates(bpa_sampler_t *, double * mui /* [nloci] or NULL */, double * mubar /* or NULL */);
+int  bpa_sampler_set_locusrate_moves(bpa_sampler_t *, double ft_mui, double ft_mubar, double a_mui, double a_mubar, double b_mubar, double mubar);
+int  bpa_sampler_locusrate_counters(bpa_sampler_t *, unsigned long prop[2], unsigned long acc[2]);
 /* measurement: HIP start/stop events on every stride-th launch of the sampler's likelihood-carrying kernels
    (stride 0 = off); bpa_sampler_timing returns the milliseconds and launch counts accumulated since, by kind: the
    sweep (the per-locus GAGE + GSPR proposals of an iteration, one launch) and the all-loci steps (TAU, MIX)       */

@@ -250,6 +250,13 @@ static inline A00_HD double a00_theta_lnacc(long k, double T, double told, doubl
 {
   return (k*(log(2.0/tnew) - log(2.0/told)) - (T/tnew - T/told)) + ((a - 1)*log(tnew/told) - b*(tnew - told));
 }
+/* ln of the acceptance ratio of a proposal for the mean of the loci's rates (prop_locusrate_mubar, stree.c:9789-9798):
+   Jacobian of the log-scale window + the gamma(a_mubar, b_mubar) prior's ratio + the L rates' gamma(a_mui, b = a_mui/mubar)
+   densities, which change through b only: L a_mui log(b'/b) - (b' - b) sum_i mu_i.  One statement of the expression for the host
+   driver (C) and the device kernel (a macro: host and device code take it as it is) */
+#define A00_MUBAR_LNACC(l_old, l_new, m_old, m_new, b_old, b_new, a_mui, a_mubar, b_mubar, nloci, sum_mui) \
+  ((((l_new) - (l_old)) + (((a_mubar) - 1)*log((m_new)/(m_old)) - (b_mubar)*((m_new) - (m_old)))) + \
+   ((nloci)*(a_mui)*log((b_new)/(b_old)) - ((b_new) - (b_old))*(sum_mui)))
 static inline A00_HD double a00_theta_gibbs_hastings(double a1, double b1, double told, double tnew)
 {
   return (-a1 - 1)*log(told/tnew) - b1*(1/told - 1/tnew);
@@ -417,6 +424,27 @@ int            a00_get_subst_model(const a00_driver_t *, unsigned i, double * fr
 /* window widths (0 = that move is off; all off by default) and the gamma(a, b) prior on alpha ('alphaprior = a b ncat') */
 void           a00_set_subst_moves(a00_driver_t *, double ft_freqs, double ft_qrates, double ft_alpha, double alpha_a, double alpha_b);
 int            a00_backend_hip_params(void * ctx /* a00_hip_ctx_t* */, unsigned locus, int which, const double * values, unsigned n);
+
+/* ---- per-locus mutation rates: BPP's 'locusrate = 1 a_mubar b_mubar a_mui iid' under the strict clock (the conditional-iid,
+   "hierarchical" prior: mu_i ~ gamma(a_mui, a_mui/mubar), mubar ~ gamma(a_mubar, b_mubar)).  Every branch length handed to the
+   likelihood back-end is (t_parent - t_child) mu_i (locus.c:2350); the MSC density does not see the rates.  cmd_run runs the
+   two moves after the substitution-parameter moves (method.c:5745-5773):
+     MUI     every locus: sliding window on log mu_i, reflected into (-99, 99); window and acceptance number from the locus's
+             own stream; lnacc = delta log mu_i + (a_mui - 1) log(mu_i'/mu_i) - (a_mui/mubar)(mu_i' - mu_i) + delta lnL; every
+             P-matrix and every partial of the locus again                                   (prop_locusrate_mui, stree.c:9225)
+     MUBAR   ONE decision: sliding window on log mubar from the global stream (window, then the acceptance number), A00_MUBAR_LNACC
+             above; no likelihood work.  a_mubar = b_mubar = 0: mubar is fixed (cfile.c:2903; the program then uses 1), the step
+             does not run and draws nothing                                                (prop_locusrate_mubar, stree.c:9770)
+   a00_set_locus_rates: the starting (or, with ft_mui = 0, fixed: the program's rates from a file) rates of all loci, each > 0 and
+   finite, before a00_initialize; 0 on a bad rate or a driver already initialized.  Never called: every rate is 1 and nothing
+   of a trajectory changes.  a00_set_locusrate_moves: window widths (0 = that move is off; both off by default), the priors'
+   parameters (a_mui > 0 when a move is on) and mubar (> 0: set it; 0: keep the current one) — at any time, as the other
+   set_* calls; 0 on a bad argument.  The two moves' proposals and acceptances are counted apart from a00_counters'
+   totals: a00_locusrate_counters, index 0 = MUI, 1 = MUBAR.                                                                     */
+int            a00_set_locus_rates(a00_driver_t *, const double * mui /* [nloci] */);
+void           a00_get_locus_rates(const a00_driver_t *, double * mui /* [nloci] or NULL */, double * mubar /* or NULL */);
+int            a00_set_locusrate_moves(a00_driver_t *, double ft_mui, double ft_mubar, double a_mui, double a_mubar, double b_mubar, double mubar);
+void           a00_locusrate_counters(const a00_driver_t *, unsigned long prop[2], unsigned long acc[2]);
 
 /* start-up evaluation: all matrices, all partials, lnL (method.c:4285-4297) */
 int            a00_initialize(a00_driver_t *);
