@@ -377,10 +377,15 @@ __device__ __forceinline__ WgBase & wg_base()
   return *reinterpret_cast<WgBase *>(smem);
 }
 __device__ __forceinline__ double prog_qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-// lgamma(a) from log(a) (Stirling's series: |error| < 1e-16 from 16 on), so that it shares a log call with its neighbours
+// The decisions' cold fall-backs are CALLS, made by the control wave alone (and by gsm::gdec_kernel's one wave).  Inlined, the
+// ~30 double coefficients of every copy of lgamma are invariants of the iteration loop, each in a register pair of its own:
+// iter_kernel<4, true, true> spilled 60 registers for them and reloaded them one by one, a wait behind each, inside every decision.
+__device__ __noinline__ double prog_lgamma_small(double a) { return lgamma(a); }
+// lgamma(a) from log(a) (Stirling's series: |error| < 1e-16 from 16 on), so that it shares a log call with its neighbours.
+// A lane without a population (a = NaN: nobody reads its value) takes the series too, not the library's path.
 __device__ __forceinline__ double lgamma_with_log(double a, double la)
 {
-  if (!(a >= 16.0)) return lgamma(a);
+  if (a < 16.0) return prog_lgamma_small(a);
   const double r = 1.0/a, r2 = r*r;
   const double ser = r*(1.0/12 - r2*(1.0/360 - r2*(1.0/1260 - r2*(1.0/1680 - r2*(1.0/1188)))));
   return ((a - 0.5)*la - a) + (0.91893853320467274178 + ser);
@@ -390,6 +395,20 @@ __device__ __forceinline__ double prog_lcg(uint32_t & z)                   // a0
   z = z*69069u + 1u;
   if (z == 0u) z = 12345671u;
   return (double)z*(1.0/4294967296.0);
+}
+// draw_gammas' way back (below; about one block in a hundred): the block's variates one after the other, the stream from the
+// block's start.  A call for the same reason as prog_lgamma_small (a00_bpp_rndgamma: square roots, logarithms, pow).
+struct GammasRedo { double g; uint32_t z; };
+__device__ __noinline__ GammasRedo prog_gammas_redo(uint32_t z, uint32_t lane, unsigned long long list, int n, uint32_t want, double shape, double g)
+{
+  for (int i = 0; i < n; ++i)
+  {
+    const uint32_t p = (uint32_t)(list >> (4*i)) & 15u;
+    if (!((want >> p) & 1u)) continue;
+    const double gi = a00_bpp_rndgamma(&z, __shfl(shape, (int)p, 64));
+    if (lane == p) g = gi;
+  }
+  return GammasRedo{g, z};
 }
 // gamma(shape, 1) variates for the populations of `list` (4 bits each, n entries) whose bit is set in `want`, from the global
 // stream in list order, exactly the numbers a00_bpp_rndgamma (legacy_rndgamma, random.c:240-275: Marsaglia-Tsang on the
@@ -437,14 +456,8 @@ __device__ __forceinline__ double draw_gammas(uint32_t & zz, uint32_t lane, unsi
   }
   if (!scan_ok || __any(mine && !ok))
   {
-    z = z0;
-    for (int i = 0; i < n; ++i)
-    {
-      const uint32_t p = (uint32_t)(list >> (4*i)) & 15u;
-      if (!((want >> p) & 1u)) continue;
-      const double gi = a00_bpp_rndgamma(&z, __shfl(shape, (int)p, 64));
-      if (lane == p) g = gi;
-    }
+    const GammasRedo r = prog_gammas_redo(z0, lane, list, n, want, shape, g);
+    z = r.z; g = r.g;
   }
   zz = z;
   return g;
