@@ -1221,6 +1221,7 @@ struct bpa_sampler
   int v2_retries = 0;                   // persistent launches that timed out in a row (sampler_download runs their iterations again)
   bool v2_prog = false;                 // ... with the program's moves: wave 0 of every workgroup is the control wave (no loci)
   unsigned v2_nwaves = 0, v2_nwg = 0, v2_lwaves = 0;
+  bool v2_sched_on = false; DevBuf<smp2::Sched> v2_sched;       // the sweep's schedule (bpa_sweep_schedule); on: sets change waves
   size_t v2_lds = 0;
   DevBuf<uint32_t> v2_wave_off;
   DevBuf<smp2::Loc> v2_loc;
@@ -1393,7 +1394,7 @@ extern "C" void bpa_sampler_destroy(bpa_sampler_t * s)
   s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free();
   s->b_dev.free(); s->b_undo.free(); s->b_thr.free();
   s->g_ops20.free(); s->g_oprng.free(); s->g_root20.free(); s->g_mtask.free(); s->g_mpm.free(); s->g_tlocus.free(); s->g_tpat.free(); s->g_ttask.free(); s->g_tn0.free(); s->g_rscaler.free();
-  s->v2_wave_off.free(); s->v2_loc.free(); s->v2_pat.free(); s->v2_xbuf.free(); s->v2_grng.free(); s->v2_err.free(); s->v2_prof.free(); s->v2_declog.free(); s->v2_sp.free();
+  s->v2_wave_off.free(); s->v2_loc.free(); s->v2_pat.free(); s->v2_xbuf.free(); s->v2_grng.free(); s->v2_err.free(); s->v2_prof.free(); s->v2_sched.free(); s->v2_declog.free(); s->v2_sp.free();
   delete s;
 }
 
@@ -1529,6 +1530,132 @@ template <int NT> static size_t v2_lds_base(bool prog)
 {
   return ((sizeof(smp2::WgLDS<NT>) + 15) & ~(size_t)15) + sizeof(smp2::WaveLDS<NT>)*(size_t)(smp2::Cfg<NT>::WAVES - (prog ? 1 : 0));
 }
+// ... where sets change waves inside the sweep: a block and a parking record for each of the workgroup's L waves of loci
+template <int NT> static size_t v2_lds_handover(unsigned L)
+{
+  return ((sizeof(smp2::WgLDS<NT>) + 15) & ~(size_t)15) + (sizeof(smp2::WaveLDS<NT>) + (size_t)smp2::Cfg<NT>::PARK*64*sizeof(uint32_t))*(size_t)L;
+}
+
+// ---- the sweep's schedule (sweep2.hpp: Sched).  The roles of a workgroup with L waves of loci on a CU's four SIMDs: L - 4 pairs
+// (older, younger), the other waves alone; a younger wave's step costs cost_young while its older partner runs and cost_alone
+// otherwise, everybody else's cost_alone.  hand_overs = 0: the identity schedule; 1 .. 3: see bpa_sweep_schedule.  A schedule
+// that the event simulation below does not find shorter than the identity is not returned: the identity is.
+struct SweepSim { double makespan; bool ok; };
+static SweepSim sweep_simulate(const smp2::Sched & sc, unsigned steps, double c_alone, double c_young)
+{
+  const unsigned R = sc.nroles, nalone = R - 2u*sc.npairs;
+  struct Lane { unsigned seg, left, done_total; double frac; bool waiting, finished; int set; } ln[8];
+  double parked_at[8][smp2::SCHED_SEGS]; int parked_set[8][smp2::SCHED_SEGS]; unsigned set_steps[8];
+  for (unsigned r = 0; r < 8; ++r) for (int k = 0; k < smp2::SCHED_SEGS; ++k) { parked_at[r][k] = -1; parked_set[r][k] = -1; }
+  auto seg_steps = [&](unsigned r, unsigned seg, unsigned done) { return seg + 1u < sc.nseg && done + sc.n[r][seg] < steps ? (unsigned)sc.n[r][seg] : steps - done; };
+  for (unsigned r = 0; r < R; ++r) { set_steps[r] = 0; ln[r] = Lane{0, seg_steps(r, 0, 0), 0, 0.0, false, false, (int)r}; }
+  double t = 0;
+  for (unsigned guard = 0; guard < 4096; ++guard)
+  {
+    // lanes at a segment's end: park, then take (possibly waiting)
+    bool moved = true;
+    while (moved)
+    {
+      moved = false;
+      for (unsigned r = 0; r < R; ++r)
+      {
+        Lane & l = ln[r];
+        if (l.finished) continue;
+        if (!l.waiting && l.left == 0)
+        {
+          if (l.seg + 1u >= sc.nseg) { l.finished = true; moved = true; continue; }
+          ++l.seg;
+          if (sc.src[r][l.seg] != r) { parked_at[r][l.seg] = t; parked_set[r][l.seg] = l.set; l.set = -1; l.waiting = true; }
+          else l.left = seg_steps(r, l.seg, set_steps[l.set]);
+          moved = true;
+        }
+        if (l.waiting)
+        {
+          const unsigned src = sc.src[r][l.seg];
+          if (src < R && parked_at[src][l.seg] >= 0 && parked_set[src][l.seg] >= 0)
+          {
+            l.set = parked_set[src][l.seg]; parked_set[src][l.seg] = -1; l.waiting = false;
+            l.left = seg_steps(r, l.seg, set_steps[l.set]);
+            moved = true;
+          }
+        }
+      }
+    }
+    // rates, the next completion
+    double dt = -1; double rate[8];
+    bool any = false;
+    for (unsigned r = 0; r < R; ++r)
+    {
+      const Lane & l = ln[r];
+      rate[r] = 0;
+      if (l.finished || l.waiting || l.left == 0) continue;
+      double c = c_alone;
+      if (r >= nalone && ((r - nalone) & 1u)) { const Lane & o = ln[r - 1]; if (!(o.finished || o.waiting || o.left == 0)) c = c_young; }
+      rate[r] = 1.0/c; any = true;
+      const double need = (1.0 - l.frac)/rate[r];
+      if (dt < 0 || need < dt) dt = need;
+    }
+    if (!any)
+    {
+      bool all = true;
+      for (unsigned r = 0; r < R; ++r) all = all && ln[r].finished;
+      if (!all) return SweepSim{0, false};                       // somebody waits for a set nobody parks
+      for (unsigned r = 0; r < R; ++r) if (set_steps[r] != steps) return SweepSim{0, false};
+      return SweepSim{t, true};
+    }
+    t += dt;
+    for (unsigned r = 0; r < R; ++r)
+      if (rate[r] > 0)
+      {
+        Lane & l = ln[r];
+        l.frac += dt*rate[r];
+        if (l.frac >= 1.0 - 1e-12) { l.frac = 0; --l.left; ++set_steps[l.set]; }
+      }
+  }
+  return SweepSim{0, false};
+}
+extern "C" int bpa_sweep_schedule(unsigned lwaves, unsigned steps, double cost_alone, double cost_young, unsigned hand_overs, unsigned char * out)
+{
+  if (!out || lwaves < 1 || lwaves > 8 || steps < 1 || steps > 255 || !(cost_alone > 0) || !(cost_young >= cost_alone)) return 0;
+  smp2::Sched id{};
+  const unsigned npairs = lwaves > 4 ? lwaves - 4 : 0, nalone = lwaves - 2*npairs;
+  id.nseg = 1; id.nroles = (uint8_t)lwaves; id.npairs = (uint8_t)npairs;
+  for (unsigned r = 0; r < 8; ++r) for (int k = 0; k < smp2::SCHED_SEGS; ++k) { id.src[r][k] = (uint8_t)r; id.n[r][k] = 0; }
+  for (unsigned r = 0; r < lwaves; ++r) id.n[r][0] = (uint8_t)steps;
+  if (hand_overs > 3) return 0;
+  // a chain of m = hand_overs swaps for every pair that has m alone waves A_0 .. A_m-1 to itself: the younger wave Y runs ONE
+  // step of whatever set it holds and passes it on — its own to A_0, A_0's to A_1, ... —, the last one it gets it finishes.
+  // A_i runs (i + 1)(1 + d) steps of its own set before it gives it to Y, so every alone wave runs d steps more than a sweep's
+  // and Y m d fewer; d = the count the simulation finds shortest.
+  smp2::Sched sc = id; double best = 0;
+  const unsigned m = hand_overs, groups = m ? std::min(nalone/m, npairs) : 0u;
+  if (groups)
+  {
+    const SweepSim t_id = sweep_simulate(id, steps, cost_alone, cost_young);
+    best = t_id.ok ? t_id.makespan : 0;
+    for (unsigned d = 1; m*(1 + d) < steps; ++d)
+    {
+      smp2::Sched c = id;
+      c.nseg = (uint8_t)(m + 1);
+      for (unsigned j = 0; j < groups; ++j)
+      {
+        const unsigned y = nalone + 2*j + 1;
+        for (unsigned i = 0; i < m; ++i)
+        {
+          const unsigned ai = j*m + i, q = (i + 1)*(1 + d);
+          c.n[y][i] = 1; c.src[y][i + 1] = (uint8_t)ai; c.n[y][i + 1] = i + 1 < m ? 1 : (uint8_t)(steps - q);
+          c.n[ai][0] = (uint8_t)q;
+          for (unsigned k = 1; k <= i; ++k) c.n[ai][k] = 0;                 // (keeps its set: its steps are counted in segment 0)
+          c.src[ai][i + 1] = (uint8_t)y; c.n[ai][i + 1] = (uint8_t)(steps - (i ? i*(1 + d) + 1 : 1));
+        }
+      }
+      const SweepSim t = sweep_simulate(c, steps, cost_alone, cost_young);
+      if (t.ok && t_id.ok && t.makespan < best) { best = t.makespan; sc = c; }
+    }
+  }
+  std::memcpy(out, &sc, sizeof sc);
+  return sc.nseg;
+}
 // the program's moves (BPP's kernel + bpa_sampler_set_program_moves + a theta prior + a theta to move): the persistent kernel's
 // form with a control wave per workgroup
 static bool v2_wants_prog(const bpa_sampler * s)
@@ -1590,25 +1717,42 @@ static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & 
   // issue slots: the pair takes a third longer than a wave alone) — 4 where the loci allow, i.e. up to 4 x 8 x CUs loci
   const unsigned nwaves = (unsigned)woff.size() - 1;
   const unsigned LMAX = WAVES - (prog ? 1u : 0u), ncu = (unsigned)std::max(prop.multiProcessorCount, 1);
-  unsigned LWAVES = (LMAX > 4u && nwaves <= 4u*ncu) ? 4u : LMAX;
-  if (const char * ev = BPA_EXP_SWITCH("BPA_SMP_LWAVES")) { const unsigned v = (unsigned)std::atoi(ev); if (v >= 1 && v <= LMAX) LWAVES = v; }     // (experiments)       // (a pair in every workgroup anyway beyond that: then as few workgroups as possible)
+  // ... and 5 where 5 still give every workgroup a CU and the sets can take turns on the younger wave of the one pair (the
+  // program's moves, four tips: 10 000 loci are 250 workgroups, one pair and three waves of loci alone each).  Fewer waves a
+  // workgroup are more workgroups at the exchange: on the identity schedule 5 are slower than LMAX (NOTES §17), so beyond
+  // that it stays LMAX — as few workgroups as possible, a pair on every SIMD anyway
+  unsigned LWAVES = (LMAX > 4u && nwaves <= 4u*ncu) ? 4u : (prog && NT == 4 && LMAX >= 5u && nwaves <= 5u*ncu) ? 5u : LMAX;
+  // BPA_SMP_DBG & 4096: deal densely — as few workgroups as hold the waves, evenly filled (LMAX or fewer waves: one workgroup
+  // of all of them), so that a few dozen loci run in pairs and hand sets over
+  if (s->env_dbg & 4096u) { const unsigned g = (nwaves + LMAX - 1)/LMAX; LWAVES = std::max((nwaves + g - 1)/std::max(g, 1u), 1u); }
+  if (const char * ev = BPA_EXP_SWITCH("BPA_SMP_LWAVES")) { const unsigned v = (unsigned)std::atoi(ev); if (v >= 1 && v <= LMAX) LWAVES = v; }     // (experiments)
   const unsigned nwg = (nwaves + LWAVES - 1)/LWAVES;
   // every workgroup must be resident (they wait for each other's sums): one per CU — a workgroup takes most of a CU's LDS
-  const size_t base = NT == 4 ? v2_lds_base<4>(prog) : v2_lds_base<8>(prog);
+  // sets change waves where a schedule is measured to win: the program's moves, four tips, 5 waves of loci — a chain of three
+  // hand-overs (NOTES §17; the two step costs, in thousands of cycles, as measured there).
+  // BPA_SMP_DBG & 8192: the identity schedule all the same (the A/B on one build); bits 14-15: 1 .. 3 = that many hand-overs
+  smp2::Sched sched{};
+  const unsigned nprop_sweep = s->env_gage >= 0 ? (unsigned)(s->env_gage + s->env_gspr) : (unsigned)(3*s->maxtips - 3);
+  // the two step costs in thousands of cycles, as NOTES §17 measured them: a wave served first, the younger wave of a pair while the older runs
+  constexpr double SWEEP_STEP_ALONE = 11.9, SWEEP_STEP_YOUNG = 18.1;
+  bool sched_on = false;
+  if (prog && NT == 4 && LWAVES == 5 && !(s->env_dbg & 8192u) && nprop_sweep <= 255u)
+    sched_on = bpa_sweep_schedule(LWAVES, nprop_sweep, SWEEP_STEP_ALONE, SWEEP_STEP_YOUNG, ((s->env_dbg >> 14) & 3u) ? (s->env_dbg >> 14) & 3u : 3u, reinterpret_cast<unsigned char *>(&sched)) > 1;
+  const size_t base = sched_on ? v2_lds_handover<4>(LWAVES) : NT == 4 ? v2_lds_base<4>(prog) : v2_lds_base<8>(prog);
   const size_t lds_max = std::min<size_t>((size_t)prop.sharedMemPerBlock > 65536 ? (size_t)prop.sharedMemPerBlock : 160*1024, 160*1024) - 256;
   if (base > lds_max) return 1;
   // (the LDS decides how many workgroups a CU holds; two waves per SIMD at most are counted on)
   const unsigned per_cu = (unsigned)std::min<size_t>(std::max<size_t>(lds_max/base, 1), 8/WAVES ? 8/WAVES : 1);
   if (nwg > per_cu*(unsigned)prop.multiProcessorCount) return 1;
   s->v2_lds = base;
-  s->v2_nt = NT; s->v2_nwaves = nwaves; s->v2_nwg = nwg; s->v2_prog = prog; s->v2_lwaves = LWAVES;
+  s->v2_nt = NT; s->v2_nwaves = nwaves; s->v2_nwg = nwg; s->v2_prog = prog; s->v2_lwaves = LWAVES; s->v2_sched_on = sched_on;
   const int zero2v[3] = {0, 0, 0};
   if (!upload(s->v2_wave_off, woff.data(), woff.size()) || !upload(s->v2_loc, loc.data(), loc.size()) ||
       !upload(s->v2_pat, pat.data(), pat.size()) || !s->v2_xbuf.reserve((size_t)2*smp2::XN) || !s->v2_grng.reserve(1) ||
-      !upload(s->v2_err, zero2v, 3) || !s->v2_prof.reserve(40 + (size_t)nwg) || !s->v2_declog.reserve(4*2048) || !s->v2_sp.reserve(1) || !s->v2_pj.reserve(16))
+      !upload(s->v2_err, zero2v, 3) || !s->v2_prof.reserve(64 + (size_t)nwg) || !upload(s->v2_sched, &sched, 1) || !s->v2_declog.reserve(4*2048) || !s->v2_sp.reserve(1) || !s->v2_pj.reserve(16))
     return 0;
   HIPCHK(hipMemset(s->v2_pj.p, 0, 16*sizeof(unsigned long long)));
-  HIPCHK(hipMemset(s->v2_prof.p, 0, (40 + (size_t)nwg)*sizeof(double)));
+  HIPCHK(hipMemset(s->v2_prof.p, 0, (64 + (size_t)nwg)*sizeof(double)));
   {
     void (*k0)(const smp2::Args) = NT == 4 ? smp2::iter_kernel<4, false> : smp2::iter_kernel<8, false>;
     void (*k1)(const smp2::Args) = NT == 4 ? smp2::iter_kernel<4, true> : smp2::iter_kernel<8, true>;
@@ -1616,6 +1760,11 @@ static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & 
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->v2_lds));
     void (*k2)(const smp2::Args) = NT == 4 ? smp2::iter_kernel<4, true, true> : smp2::iter_kernel<8, true, true>;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->v2_lds));
+    if (sched_on)
+    {
+      void (*k3)(const smp2::Args) = smp2::iter_kernel<4, true, true, true>;
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k3), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->v2_lds));
+    }
   }
   std::memset(&s->v2_sp_sent, 0xff, sizeof s->v2_sp_sent);       // (nothing sent yet)
   s->v2_ok = true;
@@ -2129,7 +2278,8 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
   const unsigned x_theta = !theta_mask ? 0u : program ? (2u*(unsigned)__builtin_popcount(theta_mask) + (merged ? 5u : 0u) + XV - 1u)/XV : ((unsigned)npop + XV - 1u)/XV;
   const unsigned x_per_iter = allloci ? x_theta + (unsigned)(npop - S) - (merged ? 1u : 0u) + 1u : 0u;
   const unsigned draws_per_iter = allloci ? 2u*(unsigned)__builtin_popcount(theta_mask) + 2u*(unsigned)(npop - S) + 2u : 0u;
-  void (*kern)(const smp2::Args) = s->v2_prog   ? (s->v2_nt == 4 ? smp2::iter_kernel<4, true, true> : smp2::iter_kernel<8, true, true>)
+  void (*kern)(const smp2::Args) = s->v2_sched_on ? smp2::iter_kernel<4, true, true, true>      // (sets change waves: four tips, the program's moves)
+                                 : s->v2_prog   ? (s->v2_nt == 4 ? smp2::iter_kernel<4, true, true> : smp2::iter_kernel<8, true, true>)
                                  : s->kernel_bpp ? (s->v2_nt == 4 ? smp2::iter_kernel<4, true> : smp2::iter_kernel<8, true>)
                                                  : (s->v2_nt == 4 ? smp2::iter_kernel<4, false> : smp2::iter_kernel<8, false>);
   const unsigned bs = s->v2_nt == 4 ? smp2::Cfg<4>::BS : smp2::Cfg<8>::BS;
@@ -2146,6 +2296,7 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
     a.counters = s->counters.p; a.lograt = s->lograt.p; a.pop_nc = s->pop_nc.p; a.pop_t2h = s->pop_t2h.p;
     a.ntasks = s->nloci; a.nwaves = s->v2_nwaves; a.nwg = s->v2_nwg; a.lwaves = s->v2_lwaves; a.xbuf = s->v2_xbuf.p;
     a.err = s->v2_err.p; a.grng = s->v2_grng.p; a.niter = chunk; a.pj = s->v2_pj.p;
+    a.sched = s->v2_sched.p; a.sched_on = s->v2_sched_on ? 1u : 0u;
     a.nsteps_gage = s->maxtips - 1; a.nsteps_gspr = 2*s->maxtips - 2;
     if (s->env_gage >= 0) { a.nsteps_gage = (uint32_t)s->env_gage; a.nsteps_gspr = (uint32_t)s->env_gspr; }
     a.theta_mask = theta_mask; a.do_allloci = allloci ? 1u : 0u; a.dbg = s->env_dbg;
@@ -2320,6 +2471,14 @@ static int sampler_download(bpa_sampler * s)
       fprintf(stderr, "[smp2] sweep cycles of the waves of workgroup 0:");
       for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", p2[8 + w]);
       fprintf(stderr, "\n");
+      double p3[17]; HIPCHK(hipMemcpy(p3, s->v2_prof.p + 40 + s->v2_nwg, sizeof p3, hipMemcpyDeviceToHost));
+      fprintf(stderr, "[smp2] %u waves of loci a workgroup, sets change waves: %s%s", s->v2_lwaves, s->v2_sched_on ? "yes" : "no", s->v2_sched_on ? "; cycles waited at hand-overs:" : "\n");
+      if (s->v2_sched_on) {
+      for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", p3[w]);
+      fprintf(stderr, " | sweeps of the last wave to reach B1: %.0f | SIMD:role of the waves:", p3[8]);
+      for (int w = 0; w < 8; ++w) { const unsigned v = (unsigned)p3[9 + w]; fprintf(stderr, " %u:%d%s", v & 15u, ((v >> 4) & 255u) == 255u ? -1 : (int)((v >> 4) & 255u), (v & 0x1000u) ? "*" : ""); }
+      fprintf(stderr, "\n");
+      }
       if (s->v2_prog)
         fprintf(stderr, "[smp2] (program-moves kernel: the numbers above are the control wave's — before B1 | wait for the loci | push | poll | THETA decision | TAU decisions | MIX decision | next proposal)\n");
     }

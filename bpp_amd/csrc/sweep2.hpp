@@ -45,6 +45,7 @@ template <int NT> struct Cfg
 #endif
   static constexpr int WAVES = NT <= 4 ? SMP2_WAVES : 4;      // per workgroup: 64 / 16 loci
   static constexpr int BS    = 64*WAVES;
+  static constexpr int PARK  = 28 + 4*W;             // dwords a lane of a set's parking record (iter_kernel: park / pick_up)
   static_assert(G == NN, "lane i of a group is node i");
 };
 
@@ -55,6 +56,14 @@ struct Loc                               // per locus, constant over the run (fl
   uint32_t np, tips, pat_off, pad;
   int8_t gl[16];                         // gene tips below each population
 };
+
+// The sweep's schedule (bpa_sweep_schedule, sampler.hpp).  A SET is the loci one wave loads (their WaveLDS block + ~40 dwords a lane
+// of registers); a wave is pinned to its SIMD, a set is not pinned to its wave.  Waves are named by ROLE — what they share their SIMD
+// with: roles 0 .. nalone - 1 have it to themselves (or share it with a wave that has no loci), then (older, younger) for every
+// pair of loci waves on one SIMD.  Role r runs nseg segments: in segment k it takes the set role src[r][k] held in segment k - 1
+// (its own: src = r) and runs n[r][k] of the set's per-locus steps.  nseg = 1: every wave keeps its set (the identity schedule).
+struct Sched { uint8_t nseg, nroles, npairs, pad; uint8_t src[8][4], n[8][4]; };
+constexpr int SCHED_SEGS = 4;
 
 struct Args
 {
@@ -83,6 +92,7 @@ struct Args
   unsigned char * const * peers; unsigned char * mail; int32_t rank, world; unsigned long long slot_bytes, seq0, spin_limit; int * p2p_err;
   const Species * sp;                    // (device memory: by value it would sit in ~50 SGPRs for the whole launch)
   unsigned long long * pj;               // proposals / accepted by move type since the host last cleared them (bpa_sampler_adapt_finetune): gage, gspr, tau, mix, theta window
+  const Sched * sched; uint32_t sched_on; // sched_on: sets change waves inside the sweep — the workgroup's LDS then holds lwaves blocks and, behind them, lwaves parking records
 };
 
 constexpr int XN = 128;                  // words per accumulator set: 8 shards x (15 sums + the arrival counter) = 8 x 128 bytes
@@ -131,7 +141,11 @@ template <int NT> struct WgLDS : WgBase
   unsigned long long xprev[2][XN];               // wave 0: every word of either accumulator set as its previous use left it
   long long prof[24];                            // BPA_SMP_DBG & 16: cycle counters of thread 0 of workgroup 0
   long long wsweep[16];                          // BPA_SMP_DBG & 16: sweep cycles of every wave of workgroup 0
+  uint32_t roles[8];                             // BPA_SMP_DBG & 16: SIMD | role << 4 | (sets change waves) << 12 of every wave of workgroup 0
   uint32_t xcoarse_, late_;                      // late_: another workgroup gave up in this launch (read from Args::err before the store)
+  uint32_t simd[8];                              // the SIMD every wave of the workgroup runs on (read once at entry)
+  uint32_t handoff[8][SCHED_SEGS];               // [role][segment]: (iteration x SCHED_SEGS + segment + 1) << 4 | the set the role parked before that segment
+  unsigned long long b1abs; long long hwait[8], b1last;                    // BPA_SMP_DBG & 16: cycles every wave of workgroup 0 waited at hand-overs; when the last of them had done its sweep
 };
 
 template <int G> __device__ __forceinline__ uint32_t gballot(bool p, uint32_t gbase)
@@ -652,9 +666,13 @@ __device__ __forceinline__ uint32_t prog_mix_redraw(uint32_t z, uint32_t theta_m
   return z;
 }
 
-template <int NT, bool BPP, bool PROG = false>
+// HO: sets change waves inside the sweep (Args::sched; launched only with Args::sched_on).  Everything of the hand-over — SIMD
+// ids, roles, park / pick-up, the segments of the sweep, the control wave's exit behind B1 — is compiled into that instance
+// alone: without it a wave's block and slot are fixed for the launch and the sweep is one loop, as they were before.
+template <int NT, bool BPP, bool PROG = false, bool HO = false>
 __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
 {
+  static_assert(!HO || PROG, "sets change waves in the program-moves kernel only");
   using C = Cfg<NT>;
   constexpr int G = C::G, LPW = C::LPW, NN = C::NN, W = C::W, NBUF = C::NBUF, NPM = C::NPM, WAVES = C::WAVES;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -663,9 +681,11 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   const uint32_t tid = threadIdx.x, wv = tid >> 6, lane = tid & 63u, b = blockIdx.x;
   const int li = (int)(lane & (uint32_t)(G - 1)); const uint32_t gbase = lane - (uint32_t)li, slot = lane/(uint32_t)G;
   // (PROG: wave 0 is the control wave — no loci, no per-wave block)
-  WaveLDS<NT> & wl = wl_all[PROG ? (wv ? wv - 1u : 0u) : wv];
-  Slot<NT> & S = wl.slot[slot];
   const uint32_t lw = PROG ? wv - 1u : wv;                       // this wave's place among the workgroup's waves of loci (PROG, wave 0: none)
+  // the SET this wave holds: its block of LDS (with hand-overs there are blocks for the waves with loci only)
+  // (HO: blocks for the waves with loci only — a wave beyond them points at block 0 and never touches it)
+  WaveLDS<NT> * wl = wl_all + (PROG ? (wv && !(HO && wv > A.lwaves) ? wv - 1u : 0u) : wv);
+  Slot<NT> * S = &wl->slot[slot];
   const uint32_t gw = lw < A.lwaves ? b*A.lwaves + lw : 0xffffffffu;       // global wave of loci
   {
     const uint32_t * src = reinterpret_cast<const uint32_t *>(A.sp);
@@ -673,6 +693,14 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     for (uint32_t i = tid; i < sizeof(Species)/4; i += C::BS) dst[i] = src[i];
     if (tid < 24u) wg.prof[tid] = 0;
     if (tid < 16u) wg.wsweep[tid] = 0;
+    if constexpr (HO)
+    {
+      if (tid < 8u) { wg.hwait[tid] = 0; wg.roles[tid] = 0xff0u; }
+      if (tid < 8u*SCHED_SEGS) (&wg.handoff[0][0])[tid] = 0u;
+      if (tid == 0) { wg.b1last = 0; wg.b1abs = 0ull; }
+      // (hardware-id register 4: SIMD_ID = bits 5:4)
+      if (lane == 0) wg.simd[wv & 7u] = (uint32_t)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);
+    }
   }
   __syncthreads();
   const Species & SP = wg.sp;
@@ -972,6 +1000,8 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
           SMP2_TICK(0);
           __syncthreads();                                              // B1: every locus's terms are in wg.accfx
           SMP2_TICK(1);
+          // a loci wave gave up at a hand-over (it raised the launch's error word): leave as after a timed-out exchange
+          if constexpr (HO) if (wg.abort_) { if (b == 0 && lane == 0) (void)atomicAdd(A.err + 1, (int)A.niter); aborted = true; __syncthreads(); __syncthreads(); break; }
           double dummy = 0;
           exchange_begin(base + (mix ? 2 : 5));
           SMP2_TICK(2);
@@ -1061,15 +1091,18 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         if (!aborted && lane < (uint32_t)(3*MAXPOP)) A.taus[lane] = wg.tau[lane];
         if (prof_on) for (int i = 0; i < 24; ++i) A.prof[(i < 16 ? 0 : (int)A.nwg) + i] = (double)wg.prof[i];
         if (prof_on) for (int i = 0; i < 16; ++i) A.prof[(int)A.nwg + 24 + i] = (double)wg.wsweep[i];
+        if (HO && prof_on) { for (int i = 0; i < 8; ++i) { A.prof[(int)A.nwg + 40 + i] = (double)wg.hwait[i]; A.prof[(int)A.nwg + 49 + i] = (double)wg.roles[i]; } A.prof[(int)A.nwg + 48] = (double)wg.b1last; }
       }
       return;
     }
   }
 
   // ---- load: the loci of this wave
+  // (what follows belongs to the SET — its block wl / S, t0 .. tips, the tree and its numbers in the registers, the per-tree
+  //  counters the store writes —, not to the wave: inside a sweep a set may change waves, park / pick_up below)
   const uint32_t t0 = gw < A.nwaves ? A.wave_off[gw] : 0u, nt = gw < A.nwaves ? A.wave_off[gw + 1] - t0 : 0u;
-  const bool act = slot < nt;
-  const uint32_t task = t0 + (act ? slot : 0u);
+  bool act = slot < nt;
+  uint32_t task = t0 + (act ? slot : 0u);
   GTree<NT> T;
   Stream<BPP> rng{0};
   double lnl_cur = 0, logpr_cur = 0;
@@ -1090,7 +1123,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     const Tree & cur = A.trees[task];               // (streams and counters survive a rejected all-loci step)
     np = L.np;
     double * g_pmat = L.pmat;
-    if (li == 0) { S.rate = L.rate; S.rw = L.rw; S.f[0] = L.f0; S.f[1] = L.f1; S.f[2] = L.f2; S.f[3] = L.f3; }
+    if (li == 0) { S->rate = L.rate; S->rw = L.rw; S->f[0] = L.f0; S->f[1] = L.f1; S->f[2] = L.f2; S->f[3] = L.f3; }
     gl_i = L.gl[li & 15];
     for (int k = 0; k < W; ++k)
     {
@@ -1101,8 +1134,8 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     const int n = 2*T.tips - 1;
     T.cf = gballot<G>(li >= T.tips && li < n && tr.clv[li] != li, gbase);
     T.pf = gballot<G>(li < n && tr.pmat[li] != li, gbase);
-    S.time[li] = li < n ? tr.time[li] : 0.0;
-    for (uint32_t i = (uint32_t)li; i < (uint32_t)(4*(2*T.tips - 2)); i += G) (&S.ab[0][0])[i] = g_pmat[i];
+    S->time[li] = li < n ? tr.time[li] : 0.0;
+    for (uint32_t i = (uint32_t)li; i < (uint32_t)(4*(2*T.tips - 2)); i += G) (&S->ab[0][0])[i] = g_pmat[i];
   }
   // pattern slots of the wave: the loci one after the other
   {
@@ -1119,19 +1152,19 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   {
     const Loc & L = A.loc[task];
     const double * g_clv = L.clv;
-    for (uint32_t q = (uint32_t)li; q < np; q += G) wl.pat[pb + q] = A.pat[L.pat_off + q];
+    for (uint32_t q = (uint32_t)li; q < np; q += G) wl->pat[pb + q] = A.pat[L.pat_off + q];
     const uint32_t nbuf = 2u*(uint32_t)(T.tips - 1);
     for (uint32_t i = (uint32_t)li; i < nbuf*np; i += G)
     {
       const uint32_t c = i/np, q = i - c*np;
       const double2 * src = reinterpret_cast<const double2 *>(g_clv + ((size_t)c*np + q)*4);
       const double2 u = src[0], w = src[1];
-      double * d = wl.clv[c][pb + q];
+      double * d = wl->clv[c][pb + q];
       d[0] = u.x; d[1] = u.y; d[2] = w.x; d[3] = w.y;
     }
   }
-  const int tips = T.tips, n = 2*tips - 1;
-  const bool inner_i = li >= tips && li < n;
+  int tips = T.tips, n = 2*tips - 1;
+  bool inner_i = li >= tips && li < n;
 
   // lane-private density state: population li of this locus
   uint32_t mync = 0; double t2h_cur = 0, t2h_new = 0;
@@ -1182,7 +1215,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     double c = 0;
     if (ncoal) c += ncoal*pl.l2t;
     if (T2h) c -= T2h/(pl.theta*1.0);
-    S.contrib_new[li] = c; t2h_new = T2h;
+    S->contrib_new[li] = c; t2h_new = T2h;
   };
   // everything a proposal leaves to do before the decision: density terms, buffer toggles, fresh (a,b), node updates,
   // the ordered sum over the patterns.  Returns the log-likelihood; lp_new = the density.
@@ -1190,19 +1223,19 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   {
     double tk[NT - 1];
 #pragma unroll
-    for (int j = 0; j < NT - 1; ++j) tk[j] = S.time[(tips + j) & (NN - 1)];
-    const double myage = S.time[li];
+    for (int j = 0; j < NT - 1; ++j) tk[j] = S->time[(tips + j) & (NN - 1)];
+    const double myage = S->time[li];
     density_counts();
     if ((pr.chain >> li) & 1u) density_term(tk);
     T.pf ^= pr.brm; T.cf ^= pr.ndm;
     if ((pr.brm >> li) & 1u)
     {
       const int par = T.parent[li];
-      const double len = (S.time[par & (NN - 1)] - myage)*1.0;                       // rate_mui = 1 (locus.c:2350)
+      const double len = (S->time[par & (NN - 1)] - myage)*1.0;                       // rate_mui = 1 (locus.c:2350)
       double a_, b_;
-      jc69_ab(len, S.rate, a_, b_);
+      jc69_ab(len, S->rate, a_, b_);
       const int pi = T.pidx(li);
-      S.ab[pi][0] = a_; S.ab[pi][1] = b_;
+      S->ab[pi][0] = a_; S->ab[pi][1] = b_;
     }
     // node updates, children first = by age: the rank of node li among the nodes to recompute
     nops = __popc(pr.ndm);
@@ -1229,7 +1262,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       {
         const uint32_t q = base + (uint32_t)li; const bool pact = q < np;
         const uint32_t ps = pb + (pact ? q : 0u);
-        const uint2 pi = wl.pat[ps];
+        const uint2 pi = wl->pat[ps];
         double last[4] = {0, 0, 0, 0}; uint32_t last_c = 0xffffffffu;
 #pragma unroll
         for (int k = 0; k < NT - 1; ++k)
@@ -1241,18 +1274,18 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
             double lv[4], rv[4], x[4], y[4];
             if (lc < (uint32_t)tips) expand_code((pi.y >> (4*lc)) & 15u, lv);
             else if (lc == last_c) { lv[0] = last[0]; lv[1] = last[1]; lv[2] = last[2]; lv[3] = last[3]; }
-            else { const double * c = wl.clv[lc - tips][ps]; lv[0] = c[0]; lv[1] = c[1]; lv[2] = c[2]; lv[3] = c[3]; }
+            else { const double * c = wl->clv[lc - tips][ps]; lv[0] = c[0]; lv[1] = c[1]; lv[2] = c[2]; lv[3] = c[3]; }
             if (rc < (uint32_t)tips) expand_code((pi.y >> (4*rc)) & 15u, rv);
             else if (rc == last_c) { rv[0] = last[0]; rv[1] = last[1]; rv[2] = last[2]; rv[3] = last[3]; }
-            else { const double * c = wl.clv[rc - tips][ps]; rv[0] = c[0]; rv[1] = c[1]; rv[2] = c[2]; rv[3] = c[3]; }
-            matvec4_ab(S.ab[lp][0], S.ab[lp][1], lv, x);
-            matvec4_ab(S.ab[rp][0], S.ab[rp][1], rv, y);
+            else { const double * c = wl->clv[rc - tips][ps]; rv[0] = c[0]; rv[1] = c[1]; rv[2] = c[2]; rv[3] = c[3]; }
+            matvec4_ab(S->ab[lp][0], S->ab[lp][1], lv, x);
+            matvec4_ab(S->ab[rp][0], S->ab[rp][1], rv, y);
             last[0] = x[0]*y[0]; last[1] = x[1]*y[1]; last[2] = x[2]*y[2]; last[3] = x[3]*y[3]; last_c = opar;
-            if (pact) { double * out = wl.clv[opar - tips][ps]; out[0] = last[0]; out[1] = last[1]; out[2] = last[2]; out[3] = last[3]; }
+            if (pact) { double * out = wl->clv[opar - tips][ps]; out[0] = last[0]; out[1] = last[1]; out[2] = last[2]; out[3] = last[3]; }
           }
         // the last update is the root's (children first, the root is the oldest node of every update list)
-        const double tr_ = dot4_pair(S.f[0], S.f[1], S.f[2], S.f[3], last);
-        if (pact) wl.term[ps] = log(0 + tr_*S.rw)*pi.x;
+        const double tr_ = dot4_pair(S->f[0], S->f[1], S->f[2], S->f[3], last);
+        if (pact) wl->term[ps] = log(0 + tr_*S->rw)*pi.x;
       }
       wsync();
       // the terms in pattern order (core_likelihood.c:206-210): eight loads in flight, then the adds (+ 0.0 past the end)
@@ -1260,7 +1293,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       {
         double v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = base + (uint32_t)j < np ? wl.term[pb + base + (uint32_t)j] : 0.0;
+        for (int j = 0; j < 8; ++j) v[j] = base + (uint32_t)j < np ? wl->term[pb + base + (uint32_t)j] : 0.0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) lnl += v[j];
       }
@@ -1272,7 +1305,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       // the density terms in population order, loads first (npop < G)
       double v[G];
 #pragma unroll
-      for (int p = 0; p < G; ++p) v[p] = p < npop ? (((pr.chain >> p) & 1u) ? S.contrib_new[p] : S.contrib[p]) : 0.0;
+      for (int p = 0; p < G; ++p) v[p] = p < npop ? (((pr.chain >> p) & 1u) ? S->contrib_new[p] : S->contrib[p]) : 0.0;
 #pragma unroll
       for (int p = 0; p < G; ++p) lp += v[p];
     }
@@ -1281,7 +1314,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   };
   auto commit_density = [&](uint32_t chain)
   {
-    if ((chain >> li) & 1u) { S.contrib[li] = S.contrib_new[li]; t2h_cur = t2h_new; }
+    if ((chain >> li) & 1u) { S->contrib[li] = S->contrib_new[li]; t2h_cur = t2h_new; }
     mync = mync_new;
   };
 
@@ -1292,7 +1325,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     wsync();
     double tk[NT - 1];
 #pragma unroll
-    for (int j = 0; j < NT - 1; ++j) tk[j] = S.time[(tips + j) & (NN - 1)];
+    for (int j = 0; j < NT - 1; ++j) tk[j] = S->time[(tips + j) & (NN - 1)];
     density_counts();
     if (li < npop) density_term(tk);
     commit_density(allpop);
@@ -1300,7 +1333,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     if (A.refresh_logpr)
     {
       double lp = 0;
-      for (int p = 0; p < npop; ++p) lp += S.contrib[p];
+      for (int p = 0; p < npop; ++p) lp += S->contrib[p];
       logpr_cur = lp;
     }
   }
@@ -1309,26 +1342,166 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   uint32_t cnt_prop = 0, cnt_acc = 0;              // all-loci proposals / accepted (the same in every workgroup)
   uint32_t cnt_gprop = 0, cnt_gacc = 0;            // of those: Gibbs draws of a theta
   uint32_t pj_tau = 0, pj_tau_acc = 0, pj_mix = 0, pj_mix_acc = 0, pj_gage = 0, pj_gage_acc = 0;
+  uint32_t step = 0;                               // the set's next per-locus step of the sweep
+
+  // ---- sets change waves (Args::sched).  The role of this wave, from the SIMDs the hardware put the workgroup's waves on: every
+  // wave derives the same table.  A placement the schedule was not made for (not Sched::npairs pairs, three loci waves on a
+  // SIMD) leaves the workgroup on the identity schedule.
+  // (role and "sets change waves" are kept in wg.roles[wave], not in registers: the step loop has none to spare)
+  if constexpr (HO)
+  {
+    uint32_t role = 0xffu; bool handover = false;
+    if (A.sched_on && lw < A.lwaves && A.lwaves <= 7u)
+    {
+      const uint32_t L = A.lwaves;
+      uint32_t nalone = 0; bool valid = true;
+      for (uint32_t x = 0; x < L; ++x)
+      {
+        uint32_t cnt = 0;
+        for (uint32_t y = 0; y < L; ++y) cnt += (y != x && wg.simd[y + 1u] == wg.simd[x + 1u]) ? 1u : 0u;
+        valid = valid && cnt <= 1u;
+        nalone += cnt == 0u ? 1u : 0u;
+      }
+      uint32_t ia = 0, ip = 0;
+      for (uint32_t x = 0; x < L; ++x)
+      {
+        int partner = -1;
+        for (uint32_t y = 0; y < L; ++y) if (y != x && wg.simd[y + 1u] == wg.simd[x + 1u]) partner = (int)y;
+        if (partner < 0) { if (x == lw) role = ia; ++ia; }
+        else if ((uint32_t)partner > x)                                  // the lower wave of a pair is the older
+        {
+          if (x == lw) role = nalone + 2u*ip;
+          if ((uint32_t)partner == lw) role = nalone + 2u*ip + 1u;
+          ++ip;
+        }
+      }
+      handover = valid && ip == (uint32_t)A.sched->npairs && nalone + 2u*ip == (uint32_t)A.sched->nroles && role < 8u;
+    }
+    if (lane == 0) wg.roles[wv & 7u] = wg.simd[wv & 7u] | (role << 4) | (handover ? 0x1000u : 0u);
+    wsync();
+  }
+  // a set's registers -> its parking record, lane by lane (record word k of lane l: [64 k + l])
+  auto park = [&]()
+  {
+    if constexpr (HO) {
+    const uint32_t myset = (uint32_t)(wl - wl_all);
+    uint32_t * r = reinterpret_cast<uint32_t *>(wl_all + A.lwaves) + (size_t)myset*(C::PARK*64) + lane;      // (the records lie behind the blocks)
+    int k = 0;
+    auto put = [&](uint32_t v) { r[64*k] = v; ++k; };
+    auto putd = [&](double v) { const unsigned long long u = (unsigned long long)__double_as_longlong(v); put((uint32_t)u); put((uint32_t)(u >> 32)); };
+#pragma unroll
+    for (int j = 0; j < W; ++j) { put(T.left.w[j]); put(T.right.w[j]); put(T.parent.w[j]); put(T.pop.w[j]); }
+    put(T.cf); put(T.pf); put((uint32_t)T.root); put((uint32_t)T.tips);
+    put((uint32_t)rng.r); put((uint32_t)((unsigned long long)rng.r >> 32));
+    putd(lnl_cur); putd(logpr_cur); putd(t2h_cur);
+    put(mync); put(np); put(pb); put((uint32_t)gl_i); put(task); put(act ? 1u : 0u);
+    put(nprop_done); put(nacc); put(w_nupd); put(w_nbr); put(a_nupd); put(a_nbr); put(a_neval); put(pj_gage); put(pj_gage_acc);
+    put(step);
+    }
+  };
+  auto pick_up = [&](uint32_t set)
+  {
+    if constexpr (HO) {
+    wl = wl_all + set; S = &wl->slot[slot];
+    const uint32_t * r = reinterpret_cast<const uint32_t *>(wl_all + A.lwaves) + (size_t)set*(C::PARK*64) + lane;
+    int k = 0;
+    auto get = [&]() { const uint32_t v = r[64*k]; ++k; return v; };
+    auto getd = [&]() { const unsigned long long lo = get(), hi = get(); return __longlong_as_double((long long)(lo | (hi << 32))); };
+#pragma unroll
+    for (int j = 0; j < W; ++j) { T.left.w[j] = get(); T.right.w[j] = get(); T.parent.w[j] = get(); T.pop.w[j] = get(); }
+    T.cf = get(); T.pf = get(); T.root = (int32_t)get(); T.tips = (int32_t)get();
+    { const unsigned long long lo = get(), hi = get(); rng.r = (a00_rng_t)(lo | (hi << 32)); }
+    lnl_cur = getd(); logpr_cur = getd(); t2h_cur = getd();
+    mync = get(); np = get(); pb = get(); gl_i = (int)get(); task = get(); act = get() != 0u;
+    nprop_done = get(); nacc = get(); w_nupd = get(); w_nbr = get(); a_nupd = get(); a_nbr = get(); a_neval = get(); pj_gage = get(); pj_gage_acc = get();
+    step = get();
+    tips = T.tips; n = 2*tips - 1; inner_i = li >= tips && li < n;
+    }
+  };
+  // Between two segments of the sweep: this wave parks its set and takes the one role `src` parked before the same segment.
+  // The parker writes the record, then (workgroup-scope release) its word of wg.handoff: the set's number under a tag made of
+  // iteration and segment — a word left by an earlier hand-over never matches.  Everybody parks before anybody waits and a
+  // wait at segment k depends on waits at earlier segments only, so the waits cannot form a cycle; and each is bounded as the
+  // exchange's are: the wall clock, the workgroup's abort word, the launch's error word.  A wave that gives up raises both
+  // words and goes on WITHOUT a set (nothing of this launch is stored: HBM keeps the state the launch started from); the
+  // control wave finds the abort word behind B1 and leaves as after a timed-out exchange.
+  auto hand_over = [&](uint32_t role, uint32_t src, uint32_t seg, uint32_t it, bool prof)
+  {
+    if constexpr (HO) {
+    const uint32_t tag = it*(uint32_t)SCHED_SEGS + seg + 1u;
+    park();
+    // (lane 0 releases what all 64 lanes wrote: a wave's LDS instructions complete in order, every lane's record words are
+    //  ahead of this store in the wave's one LDS queue and the release waits for them — the hardware's order, not the
+    //  per-thread memory model's)
+    if (lane == 0) __hip_atomic_store(&wg.handoff[role & 7u][seg & 3u], (tag << 4) | (uint32_t)(wl - wl_all), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const long long c0 = prof ? clock64() : 0;
+    const unsigned long long t_wait = wall_clock64();
+    uint32_t v = 0; bool ok = true;
+    for (uint32_t rounds = 1;; ++rounds)
+    {
+      v = __hip_atomic_load(&wg.handoff[src & 7u][seg & 3u], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if ((v >> 4) == tag) break;
+      if (__hip_atomic_load(&wg.abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) { ok = false; break; }
+      if ((rounds & 63u) == 0 && (wall_clock64() - t_wait > 50000000ull || __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) { ok = false; break; }     // 0.5 s at 100 MHz
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if (prof) wg.hwait[wv & 7u] += clock64() - c0;
+    const uint32_t set = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v & 15u));
+    if (ok && set < A.lwaves) pick_up(set);
+    else
+    {
+      if (lane == 0) { __hip_atomic_store(&wg.abort_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); (void)__hip_atomic_exchange(A.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+      act = false;
+      if (lane == 0) wg.roles[wv & 7u] &= ~0x1000u;
+    }
+    wsync();
+    }
+  };
+  // the segment `seg` of this wave's role begins: the hand-over, if the schedule has one here; returns the step the segment ends before
+  auto segment_begin = [&](uint32_t seg, uint32_t it, uint32_t nprop, bool prof) -> uint32_t
+  {
+    if constexpr (HO)
+    {
+      const uint32_t role = (wg.roles[wv & 7u] >> 4) & 7u;
+      const uint32_t nseg = A.sched->nseg, src = A.sched->src[role][seg & 3u], nrun = A.sched->n[role][seg & 3u];
+      if (seg && src != role) hand_over(role, src, seg, it, prof);
+      return (wg.roles[wv & 7u] & 0x1000u) && seg + 1u < nseg && step + nrun < nprop ? step + nrun : nprop;
+    }
+    return nprop;
+  };
   const bool declog = (A.dbg & 256u) && b == 0;    // every all-loci decision of this launch: A.declog[4 k] = what, lnacc, u, accepted
   uint32_t ndec = 0;
   const bool wgprof = (A.dbg & 32u) && tid == 0;
   long long wg_sweep = 0;
   bool aborted = false;
 
-  // (Two waves share a SIMD — wave w and w + WAVES/2 — and the pair is bound by instruction issue: a sweep asks for ~0.68 of a
-  // SIMD's issue slots, the arbiter serves the older wave first, so the older runs as if alone and the younger finishes a
-  // third later: 325 M vs 441 M cycles per 3 000 sweeps.  Priorities (s_setprio) change nothing, and making the older wait
-  // for the younger at three points of every proposal only moves both to 441 M: the SUM of their instructions is what the
-  // SIMD takes.  10 000 four-taxon loci need five waves of loci per CU, i.e. a pair in every workgroup.)
+  // (Two waves of loci on one SIMD are bound by instruction issue: a sweep asks for ~0.68 of a SIMD's issue slots and the arbiter
+  // serves the older wave first, so the older runs as if alone — 107 k cycles for the 9 steps of a four-tip sweep, 11.9 k a step —
+  // and the younger gets through a step in 18.1 k while the older runs: 143 k for its sweep.  Priorities (s_setprio) change
+  // nothing, and making the older wait for the younger at three points of every proposal only moves both to the younger's
+  // time: the SUM of their instructions is what the SIMD takes.  Which waves share a SIMD is the hardware's choice (wg.simd).
+  // 10 000 four-taxon loci are 1 250 waves on 1 024 SIMDs: no dealing avoids the pairs, but a SET need not stay on the
+  // younger wave — with five waves of loci a workgroup (one pair, three waves alone) the sets take turns on it, Args::sched:
+  // the last wave reaches B1 after 125 k cycles instead of 143 k.  NOTES 17.)
   if constexpr (PROG) __syncthreads();             // B0: the control wave's first proposal is out
   for (uint32_t it = 0; it < A.niter && !aborted; ++it)
   {
     // ================= GAGE + GSPR of every locus
-    const uint32_t nprop = A.nsteps_gage + A.nsteps_gspr;
+    // (HO: a wave beyond the workgroup's waves of loci has no set and takes none: it goes straight to the barrier, its SIMD's
+    //  issue slots are the loci wave's it shares the SIMD with)
+    const uint32_t nprop = HO && lw >= A.lwaves ? 0u : A.nsteps_gage + A.nsteps_gspr;
     const long long wg_t0 = wgprof ? clock64() : 0;
     const bool wvprof = (A.dbg & 16u) && b == 0 && lane == 0;
     const long long wv_t0 = wvprof ? clock64() : 0;
-    for (uint32_t step = 0; step < nprop; ++step)
+    // HO: the sweep in segments, between two of them the set may go to another wave.  A hand-over happens at a step boundary
+    // only: behind the wsync() that closes a step's acceptance or roll-back.  Otherwise: one pass, one loop
+    step = 0;
+    uint32_t seg = 0;
+    do
+    {
+    uint32_t seg_end = nprop;
+    if constexpr (HO) { if (wg.roles[wv & 7u] & 0x1000u) seg_end = segment_begin(seg, it, nprop, wvprof); ++seg; }
+    for (; step < seg_end; ++step)
     {
       // roll-back copies: registers, and the age of node li
       const GTree<NT> U = T;
@@ -1337,10 +1510,10 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       bool ok = false;
       if (act)
       {
-        tsave = S.time[li];
+        tsave = S->time[li];
         ok = step < A.nsteps_gage
-          ? propose_gage<NT, BPP>(T, rng, S.time, (int)step, pl, wg.anc, wg.tau, SP.ft_gage, li, gbase, pr)
-          : propose_gspr<NT, BPP>(T, rng, S.time, (int)(step - A.nsteps_gage), pl, gl_i, wg.anc, wg.tau, wg.lograt, SP.ft_gspr, li, gbase, pr);
+          ? propose_gage<NT, BPP>(T, rng, S->time, (int)step, pl, wg.anc, wg.tau, SP.ft_gage, li, gbase, pr)
+          : propose_gspr<NT, BPP>(T, rng, S->time, (int)(step - A.nsteps_gage), pl, gl_i, wg.anc, wg.tau, wg.lograt, SP.ft_gspr, li, gbase, pr);
       }
       SMP2_TICK(0);
       if (ok)
@@ -1357,14 +1530,21 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         const bool gage_step = step < A.nsteps_gage;
         pj_gage += gage_step ? 1u : 0u;
         if (rng.accept(lnacc)) { lnl_cur = lnl; logpr_cur = lp_new; ++nacc; pj_gage_acc += gage_step ? 1u : 0u; commit_density(pr.chain); }
-        else { T = U; S.time[li] = tsave; }
+        else { T = U; S->time[li] = tsave; }
         wsync();
         SMP2_TICK(2);
       }
-      else if (act) { T = U; S.time[li] = tsave; wsync(); }
+      else if (act) { T = U; S->time[li] = tsave; wsync(); }
     }
+    } while (HO && step < nprop);
+    (void)seg;
     if (wgprof) wg_sweep += clock64() - wg_t0;
-    if (wvprof) wg.wsweep[wv] += clock64() - wv_t0;
+    if (wvprof)
+    {
+      const long long t1 = clock64();
+      wg.wsweep[wv] += t1 - wv_t0;
+      if constexpr (HO) (void)__hip_atomic_fetch_max(&wg.b1abs, (unsigned long long)t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     if (!A.do_allloci) continue;
 
     // ================= TAU per species divergence, then MIX: one decision each for all loci.  A step in four parts — the
@@ -1428,7 +1608,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     auto step_locus = [&](int base)
     {
       cf0 = T.cf; pf0 = T.pf;
-      tsave = act ? S.time[li] : 0.0;
+      tsave = act ? S->time[li] : 0.0;
       lnl_new = lnl_cur; lp_new = logpr_cur;
       evaluated = false;
       if (act)
@@ -1443,7 +1623,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
           const double tk_ = tsave;
           const bool moved = inner_i && (pk == q || pk == cl || pk == cr) && !(tk_ < tq_lo || tk_ > tq_hi);
           const bool up = moved && tk_ >= tq_old;
-          if (moved) S.time[li] = up ? tq_hi + maxf*(tk_ - tq_hi) : tq_lo + minf*(tk_ - tq_lo);
+          if (moved) S->time[li] = up ? tq_hi + maxf*(tk_ - tq_hi) : tq_lo + minf*(tk_ - tq_lo);
           const uint32_t mm = gballot<G>(moved, gbase);
           const int above = __popc(gballot<G>(up, gbase)), below = __popc(mm) - above;
           const int par = T.parent[li];
@@ -1457,7 +1637,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         }
         else
         {
-          if (inner_i) S.time[li] = tsave*mix_c;
+          if (inner_i) S->time[li] = tsave*mix_c;
           pr.ndm = gballot<G>(inner_i, gbase);
           pr.brm = gballot<G>(li < n && (int)T.parent[li] >= 0, gbase);
           hast = (double)(tips - 1)*mix_lnc;
@@ -1514,17 +1694,17 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         }
       }
       if (accept) { if (act) { lnl_cur = lnl_new; logpr_cur = lp_new; commit_density(allpop); } }
-      else if (act) { T.cf = cf0; T.pf = pf0; S.time[li] = tsave; }
+      else if (act) { T.cf = cf0; T.pf = pf0; S->time[li] = tsave; }
       if constexpr (!PROG) __syncthreads();
       load_pop();
       wsync();
       if (PROG && (refresh || accept) && act)
       {
         // the densities with the thetas as they are now (THETA's decisions, a TAU's or MIX's re-draws), from the statistics of the trees as settled
-        if (li < npop) S.contrib[li] = msc_term((int)mync, t2h_cur, pl.theta, pl.l2t);
+        if (li < npop) S->contrib[li] = msc_term((int)mync, t2h_cur, pl.theta, pl.l2t);
         wsync();
         double lp = 0;
-        for (int p = 0; p < npop; ++p) lp += S.contrib[p];
+        for (int p = 0; p < npop; ++p) lp += S->contrib[p];
         logpr_cur = lp;
         wsync();
       }
@@ -1542,6 +1722,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         if (first && act && on) { fx_add(2*kidx, (double)mync, false); fx_add(2*kidx + 1, t2h_cur, false); }
         step_locus(first ? nth : 0);
         __syncthreads();                                                // B1: the terms are in
+        if constexpr (HO) if (first && wvprof && lw == 0u) wg.b1last += (long long)wg.b1abs - wv_t0;      // (the sweep of the last wave to finish it)
         __syncthreads();                                                // B3: the decision is out (and the species tree as it now is, and the next proposal)
         const bool ab = wg.abort_ != 0u;
         accept = wg.dec.acc_step != 0u;
@@ -1580,12 +1761,12 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         // acceptance numbers now, in population order, so every lane walks through all of them
         if (BPP)
         {
-          if (on) { wl.term[li] = tnew; wl.term[16 + li] = told; }
+          if (on) { wl->term[li] = tnew; wl->term[16 + li] = told; }
           wsync();
           for (int p = 0; p < npop; ++p)
             if ((A.theta_mask >> p) & 1u)
             {
-              const double tn = wl.term[p], to = wl.term[16 + p];
+              const double tn = wl->term[p], to = wl->term[16 + p];
               const double lnacc = wg.xtot[p] + ((SP.theta_alpha - 1)*log(tn/to) - SP.theta_beta*(tn - to));
               const bool acc = tn > 0 && grng.accept(lnacc);
               if (p == li) { accept = acc; my_lnacc = lnacc; }
@@ -1617,10 +1798,10 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       // every tree's density with the new thetas, from its statistics, in population order
       if (act)
       {
-        if (li < npop) S.contrib[li] = msc_term((int)mync, t2h_cur, pl.theta, pl.l2t);
+        if (li < npop) S->contrib[li] = msc_term((int)mync, t2h_cur, pl.theta, pl.l2t);
         wsync();
         double lp = 0;
-        for (int p = 0; p < npop; ++p) lp += S.contrib[p];
+        for (int p = 0; p < npop; ++p) lp += S->contrib[p];
         logpr_cur = lp;
         wsync();
       }
@@ -1675,7 +1856,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         reinterpret_cast<uint32_t *>(tr.parent)[li] = wp_; reinterpret_cast<uint32_t *>(tr.pop)[li] = wq_;
       }
     }
-    if (li < n) { tr.time[li] = S.time[li]; tr.clv[li] = (int8_t)T.cidx(li); tr.pmat[li] = (int8_t)T.pidx(li); }
+    if (li < n) { tr.time[li] = S->time[li]; tr.clv[li] = (int8_t)T.cidx(li); tr.pmat[li] = (int8_t)T.pidx(li); }
     if (li == 0)
     {
       tr.lnl = lnl_cur; tr.logpr = logpr_cur; tr.rng = rng.r; tr.root = T.root;
@@ -1686,12 +1867,12 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       (void)atomicAdd(A.pj + 2, (unsigned long long)(nprop_done - pj_gage)); (void)atomicAdd(A.pj + 3, (unsigned long long)(nacc - pj_gage_acc));
     }
     if (li < npop) { A.pop_nc[(size_t)li*A.ntasks + task] = (int8_t)mync; A.pop_t2h[(size_t)li*A.ntasks + task] = t2h_cur; }
-    for (uint32_t i = (uint32_t)li; i < (uint32_t)(4*(2*tips - 2)); i += G) g_pmat[i] = (&S.ab[0][0])[i];
+    for (uint32_t i = (uint32_t)li; i < (uint32_t)(4*(2*tips - 2)); i += G) g_pmat[i] = (&S->ab[0][0])[i];
     const uint32_t nbuf = 2u*(uint32_t)(tips - 1);
     for (uint32_t i = (uint32_t)li; i < nbuf*np; i += G)
     {
       const uint32_t c = i/np, q = i - c*np;
-      const double * d = wl.clv[c][pb + q];
+      const double * d = wl->clv[c][pb + q];
       double2 u, w; u.x = d[0]; u.y = d[1]; w.x = d[2]; w.y = d[3];
       double2 * dst = reinterpret_cast<double2 *>(g_clv + ((size_t)c*np + q)*4);
       dst[0] = u; dst[1] = w;
@@ -1710,6 +1891,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   if (b == 0 && tid < (uint32_t)(3*MAXPOP)) A.taus[tid] = wg.tau[tid];
   if (prof_on) for (int i = 0; i < 24; ++i) A.prof[(i < 16 ? 0 : (int)A.nwg) + i] = (double)wg.prof[i];
   if (prof_on) for (int i = 0; i < 16; ++i) A.prof[(int)A.nwg + 24 + i] = (double)wg.wsweep[i];
+  if (HO && prof_on) { for (int i = 0; i < 8; ++i) { A.prof[(int)A.nwg + 40 + i] = (double)wg.hwait[i]; A.prof[(int)A.nwg + 49 + i] = (double)wg.roles[i]; } A.prof[(int)A.nwg + 48] = (double)wg.b1last; }
   if (wgprof) A.prof[16 + b] = (double)wg_sweep;
 }
 

@@ -333,6 +333,18 @@ double bpa_finetune_onestep(double pjump, double finetune);
 int  bpa_sampler_adapt_finetune(bpa_sampler_t *, double * pjump, double * finetune);
 int  bpa_sampler_burnin(bpa_sampler_t *, unsigned iterations, double * finetune);
 unsigned bpa_burnin_schedule(unsigned burnin, unsigned * after, unsigned cap);
+/* The persistent iteration kernel's sweep schedule for a workgroup with `lwaves` waves of loci (1 .. 8) and `steps` per-locus
+   steps a sweep.  Waves are named by role: first those with a SIMD to themselves (lwaves <= 4: all), then (older, younger) for each
+   of the lwaves - 4 pairs on one SIMD; a younger wave's step costs cost_young while its older partner runs, everybody else's
+   cost_alone.  out receives 68 bytes: segments per role (nseg), roles, pairs, 0, then src[8][4] and n[8][4] — in segment k
+   role r takes the set of loci role src[r][k] held in segment k - 1 (its own: src = r) and runs n[r][k] of that set's steps,
+   the last segment all that are left.  hand_overs: 0 the identity schedule (nseg = 1: every wave keeps its set); m = 1 .. 3:
+   a chain of m hand-overs for every pair that has m alone waves to itself — the younger wave runs one step of its own set,
+   then one of each of the m alone waves' sets in turn, and finishes the last; alone wave i runs (i + 1)(1 + d) steps of its own
+   set, gives it to the younger wave and finishes the set that wave held before (d: the count the event simulation of the two
+   costs finds shortest); the identity is returned instead wherever the simulation does not find the schedule shorter.
+   Returns nseg, 0 for arguments out of range (hand_overs > 3 among them).                                               */
+int bpa_sweep_schedule(unsigned lwaves, unsigned steps, double cost_alone, double cost_young, unsigned hand_overs, unsigned char * out);
 /* which generator and window the moves draw from (a00_set_proposal_kernel of bpp_amd_host.h; before initialize):
    BPA_KERNEL_UNIFORM (default) our 64-bit streams, window = finetune x (u - 1/2), the acceptance number always drawn;
    BPA_KERNEL_BPP     the reference's own — legacy_rndu (random.c:104-122) and the Bactrian-Laplace variate of
