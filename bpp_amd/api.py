@@ -142,6 +142,7 @@ def lib():
         "bpa_sampler_burnin": (i, [vp, u, dp]),
         "bpa_burnin_schedule": (u, [u, C.POINTER(u), u]),
         "bpa_sweep_schedule": (i, [u, u, d, d, u, C.c_char_p]),
+        "bpa_exchange_layout": (i, [u, u, u, u, C.POINTER(u)]),
         "bpa_sampler_set_tau_prior": (None, [vp, d, d]),
         "bpa_sampler_set_theta_prior": (None, [vp, d, d, d]),
         "bpa_sampler_get_thetas": (i, [vp, dp]),
@@ -202,7 +203,7 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_experimental_build", "bpa_devi
             "bpa_plan_work", "bpa_engine_enable_timing", "bpa_engine_timing", "bpa_engine_set_timing_stride", "bpa_engine_timing_work", "bpa_engine_timing_work_codes", "bpa_plan_work_codes",
             "bpa_sampler_create", "bpa_sampler_destroy", "bpa_sampler_set_tree", "bpa_sampler_initialize",
             "bpa_sampler_set_species_tree", "bpa_sampler_set_tip_species", "bpa_sampler_set_finetune",
-            "bpa_finetune_onestep", "bpa_sampler_adapt_finetune", "bpa_sampler_burnin", "bpa_burnin_schedule", "bpa_sweep_schedule",
+            "bpa_finetune_onestep", "bpa_sampler_adapt_finetune", "bpa_sampler_burnin", "bpa_burnin_schedule", "bpa_sweep_schedule", "bpa_exchange_layout",
             "bpa_sampler_set_tau_prior", "bpa_sampler_get_taus", "bpa_sampler_get_tree_msc",
             "bpa_sampler_set_theta_prior", "bpa_sampler_get_thetas", "bpa_sampler_set_allreduce",
             "bpa_sampler_iterate", "bpa_sampler_get_tree", "bpa_sampler_summary",

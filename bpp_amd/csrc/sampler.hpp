@@ -1614,6 +1614,15 @@ static SweepSim sweep_simulate(const smp2::Sched & sc, unsigned steps, double c_
   }
   return SweepSim{0, false};
 }
+// the layout of the persistent kernel's exchange (smp2::xlayout, sweep2.hpp), for a caller on the host
+extern "C" int bpa_exchange_layout(unsigned shards, unsigned workgroup, unsigned lane, unsigned load, unsigned * out)
+{
+  if (shards < smp2::XS_MIN || shards > smp2::XS_MAX || (shards & (shards - 1u)) != 0u || lane >= 64u || load >= shards/4u || !out) return 0;
+  const smp2::XLayout L = smp2::xlayout(shards, workgroup, lane, load);
+  out[0] = L.set_words; out[1] = (unsigned)smp2::XBUF_WORDS; out[2] = L.shard; out[3] = L.word;
+  return (int)(shards/4u);
+}
+
 extern "C" int bpa_sweep_schedule(unsigned lwaves, unsigned steps, double cost_alone, double cost_young, unsigned hand_overs, unsigned char * out)
 {
   if (!out || lwaves < 1 || lwaves > 8 || steps < 1 || steps > 255 || !(cost_alone > 0) || !(cost_young >= cost_alone)) return 0;
@@ -1748,7 +1757,7 @@ static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & 
   s->v2_nt = NT; s->v2_nwaves = nwaves; s->v2_nwg = nwg; s->v2_prog = prog; s->v2_lwaves = LWAVES; s->v2_sched_on = sched_on;
   const int zero2v[3] = {0, 0, 0};
   if (!upload(s->v2_wave_off, woff.data(), woff.size()) || !upload(s->v2_loc, loc.data(), loc.size()) ||
-      !upload(s->v2_pat, pat.data(), pat.size()) || !s->v2_xbuf.reserve((size_t)2*smp2::XN) || !s->v2_grng.reserve(1) ||
+      !upload(s->v2_pat, pat.data(), pat.size()) || !s->v2_xbuf.reserve(smp2::XBUF_WORDS) || !s->v2_grng.reserve(1) ||
       !upload(s->v2_err, zero2v, 3) || !s->v2_prof.reserve(64 + (size_t)nwg) || !upload(s->v2_sched, &sched, 1) || !s->v2_declog.reserve(4*2048) || !s->v2_sp.reserve(1) || !s->v2_pj.reserve(16))
     return 0;
   HIPCHK(hipMemset(s->v2_pj.p, 0, 16*sizeof(unsigned long long)));
@@ -2263,6 +2272,8 @@ extern "C" int bpa_sampler_set_allreduce(bpa_sampler_t * s, bpa_allreduce_fn fn,
 // LDS from the first proposal to the last decision (sweep2.hpp)
 // in_kernel_allloci = false (several ranks): only the per-locus sweep of ONE iteration; the all-loci steps then run as
 // launches of sampler.hpp's kernels with the sums all-reduced in between
+// the exchange's shards per accumulator set unless BPA_SMP_DBG says otherwise (NOTES §18: the fastest of those measured at 10 000 loci)
+constexpr unsigned XSHARDS_DEFAULT = 32;
 static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kernel_allloci)
 {
   bpa_engine * e = s->eng;
@@ -2297,6 +2308,11 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
     a.ntasks = s->nloci; a.nwaves = s->v2_nwaves; a.nwg = s->v2_nwg; a.lwaves = s->v2_lwaves; a.xbuf = s->v2_xbuf.p;
     a.err = s->v2_err.p; a.grng = s->v2_grng.p; a.niter = chunk; a.pj = s->v2_pj.p;
     a.sched = s->v2_sched.p; a.sched_on = s->v2_sched_on ? 1u : 0u;
+    // the exchange's layout; BPA_SMP_DBG bits 16-18: 1 .. 4 = 8, 16, 32, 64 shards a set (anything else: the default)
+    {
+      const unsigned cs = (s->env_dbg >> 16) & 7u;
+      a.xshards = cs >= 1u && cs <= 4u ? 4u << cs : XSHARDS_DEFAULT;
+    }
     a.nsteps_gage = s->maxtips - 1; a.nsteps_gspr = 2*s->maxtips - 2;
     if (s->env_gage >= 0) { a.nsteps_gage = (uint32_t)s->env_gage; a.nsteps_gspr = (uint32_t)s->env_gspr; }
     a.theta_mask = theta_mask; a.do_allloci = allloci ? 1u : 0u; a.dbg = s->env_dbg;
@@ -2323,7 +2339,7 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
       if (!s->kernel_bpp || !s->v2_grng_sent)
         HIPCHK(hipMemcpyAsync(s->v2_grng.p, &s->grng, sizeof(a00_rng_t), hipMemcpyHostToDevice, e->stream));
       s->v2_grng_sent = true;
-      HIPCHK(hipMemsetAsync(s->v2_xbuf.p, 0, (size_t)2*smp2::XN*sizeof(unsigned long long), e->stream));
+      HIPCHK(hipMemsetAsync(s->v2_xbuf.p, 0, smp2::XBUF_WORDS*sizeof(unsigned long long), e->stream));
     }
     if (s->timing_stride && (s->timing_phase++ % s->timing_stride) == 0)
     {
@@ -2468,6 +2484,8 @@ static int sampler_download(bpa_sampler * s)
       fprintf(stderr, "[smp2] cycles of lane 0 of workgroup 0, last launch: propose %.0f evaluate %.0f decide %.0f theta %.0f tau %.0f mix %.0f | exchange: theta %.0f tau+mix %.0f | inside the exchanges: first barrier %.0f sums %.0f barrier %.0f arrival + poll %.0f last barrier %.0f | of theta / tau / mix: the decision's arithmetic after the totals %.0f %.0f, MIX's re-draws inside the wait %.0f\n",
               pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6], pr[7], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13], pr[14], pr[15]);
       double p2[24]; HIPCHK(hipMemcpy(p2, s->v2_prof.p + 16 + s->v2_nwg, sizeof p2, hipMemcpyDeviceToHost));
+      if (s->v2_prog && (s->env_dbg & 64u))
+        fprintf(stderr, "[smp2] inside the dummy exchanges (nobody late: the protocol alone): first barrier %.0f sums %.0f barrier %.0f arrival + poll %.0f last barrier %.0f\n", p2[0], p2[1], p2[2], p2[3], p2[4]);
       fprintf(stderr, "[smp2] sweep cycles of the waves of workgroup 0:");
       for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", p2[8 + w]);
       fprintf(stderr, "\n");

@@ -81,7 +81,7 @@ struct Args
   int8_t * pop_nc; double * pop_t2h;     // sufficient statistics of the final state (sampler.hpp's THETA kernels read them)
   uint32_t ntasks, nwaves, nwg;
   uint32_t lwaves;                       // waves with loci per workgroup (<= WAVES, PROG: <= WAVES - 1): fewer where the loci allow — one wave per SIMD has the SIMD to itself
-  unsigned long long * xbuf;             // [2][XN] accumulators of the all-loci steps' sums
+  unsigned long long * xbuf;             // [XBUF_WORDS] the two accumulator sets of the all-loci steps' sums, laid out by xlayout(xshards, ...)
   int * err;                             // [0] a wait timed out: the launch left everything as it found it; [1] += the iterations it did not run; [2] += all-loci steps accepted with a term summed through the coarse companion
   a00_rng_t * grng;                      // the global stream: read at entry, written back by workgroup 0
   uint32_t niter, nsteps_gage, nsteps_gspr, theta_mask, do_allloci, dbg;
@@ -93,10 +93,37 @@ struct Args
   const Species * sp;                    // (device memory: by value it would sit in ~50 SGPRs for the whole launch)
   unsigned long long * pj;               // proposals / accepted by move type since the host last cleared them (bpa_sampler_adapt_finetune): gage, gspr, tau, mix, theta window
   const Sched * sched; uint32_t sched_on; // sched_on: sets change waves inside the sweep — the workgroup's LDS then holds lwaves blocks and, behind them, lwaves parking records
+  uint32_t xshards;                      // the exchange's layout: shards per accumulator set (8 .. 64, a power of two)
 };
 
-constexpr int XN = 128;                  // words per accumulator set: 8 shards x (15 sums + the arrival counter) = 8 x 128 bytes
 constexpr int XV = 15;                   // sums per block of an exchange
+// The exchange's layout (bpa_exchange_layout, sampler.hpp).  An accumulator set is S shards; a shard is ONE 128-byte line of its
+// own, XV sums + the arrival word, one after the other.  Workgroup b adds to shard b mod S: under round-robin
+// dispatch the workgroups of one shard then share an XCD (speed only).  The poll is S/4 loads a lane: lane 16 x + k reads, as
+// its load j, word k of shard x + 4 j — every word of every shard once a round, word k only ever on the lanes with lane mod 16 = k.
+constexpr uint32_t XS_MIN = 8, XS_MAX = 64, XLINE = 16;                  // shards a set; words a line
+constexpr size_t XBUF_WORDS = (size_t)2*XS_MAX*XLINE;                    // both sets of the largest layout
+constexpr int XSLEEP_FIRST = 16;                                         // s_sleep units (64 cycles) between a workgroup's arrival and its first poll round
+struct XLayout { uint32_t set_words, shard, word; };                     // words a set; word offsets in a set: the workgroup's shard, the word of (lane, load)
+__host__ __device__ inline XLayout xlayout(uint32_t S, uint32_t b, uint32_t lane, uint32_t load)
+{
+  XLayout L;
+  L.set_words = S*XLINE;
+  L.shard = (b & (S - 1u))*XLINE;
+  L.word = ((lane >> 4) + 4u*load)*XLINE + (lane & 15u);
+  return L;
+}
+// one round of the poll: a lane's S/4 loads are all on their way before the first is waited for; their sum
+template <int NL> __device__ __forceinline__ unsigned long long xpoll_sum(const unsigned long long * p, uint32_t step)
+{
+  unsigned long long v[NL];
+#pragma unroll
+  for (int j = 0; j < NL; ++j) v[j] = __hip_atomic_load(p + (size_t)j*step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  unsigned long long s = v[0];
+#pragma unroll
+  for (int j = 1; j < NL; ++j) s += v[j];
+  return s;
+}
 
 template <int NT> struct Slot
 {
@@ -138,8 +165,8 @@ template <int NT> struct WgLDS : WgBase
   unsigned long long accfx[32];                  // this workgroup's sums of an all-loci step, 2^-44 fixed point (LDS atomics)
   uint32_t anc[16];
   uint32_t abort_, bad_, xbad_, coarse_;         // coarse_: a term of this workgroup went to the coarse companion sum; xcoarse_: of any
-  unsigned long long xprev[2][XN];               // wave 0: every word of either accumulator set as its previous use left it
-  long long prof[24];                            // BPA_SMP_DBG & 16: cycle counters of thread 0 of workgroup 0
+  unsigned long long xprev[2][64];               // wave 0: per lane, the sum of the words it polls of either accumulator set as the set's previous use left them
+  long long prof[24];                            // BPA_SMP_DBG & 16: cycle counters of thread 0 of workgroup 0 (16 .. 20: the dummy exchange's, BPA_SMP_DBG & 64)
   long long wsweep[16];                          // BPA_SMP_DBG & 16: sweep cycles of every wave of workgroup 0
   uint32_t roles[8];                             // BPA_SMP_DBG & 16: SIMD | role << 4 | (sets change waves) << 12 of every wave of workgroup 0
   uint32_t xcoarse_, late_;                      // late_: another workgroup gave up in this launch (read from Args::err before the store)
@@ -714,7 +741,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   // well: the iterations then run again IN ORDER, from the state and the random numbers the first of them started from
   if (tid == 0) { wg.abort_ = __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? 2u : 0u; wg.late_ = 0; wg.bad_ = 0; wg.xbad_ = 0; wg.coarse_ = 0; wg.xcoarse_ = 0; }
   if (tid < 32u) wg.accfx[tid] = 0ull;
-  for (uint32_t i = tid; i < 2u*XN; i += C::BS) (&wg.xprev[0][0])[i] = 0ull;
+  if (tid < 2u*64u) (&wg.xprev[0][0])[tid] = 0ull;
   PopLane pl;
   {
     pl.parent = li < npop ? (int)SP.parent[li < MAXPOP ? li : 0] : -1;
@@ -750,8 +777,12 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   // the workgroup adds those to the step's device accumulators (device-scope atomics) and then bumps the arrival
   // counter; wave 0 polls until every workgroup has arrived.  Device accumulators and counter only ever grow (the host
   // zeroes them before the launch) and two sets alternate, so a workgroup already in the next step never touches what
-  // a slower one still reads.  Up to 7 values share one 64-byte block with the counter: the poll's ONE load brings the
-  // totals with the count (they landed before the arrival was counted).  False: timed out.
+  // a slower one still reads.  A set is Args::xshards shards (xlayout), each a 128-byte line of its own — up to 15 sums and the
+  // arrival word — for the workgroups b with b mod xshards = the shard: atomics on one line are served one after the other, so
+  // the more lines, the fewer wait behind each other.  The load that brings a shard's arrival word brings its sums with it
+  // (they landed before the arrival was counted); a poll round is xshards/4 loads a lane, all issued before the first is
+  // waited for, and a lane keeps only the SUM of its words: what grew since the set's previous use is the same number mod 2^64.
+  // False: timed out.
   constexpr double FX = 1099511627776.0;             // 2^40: 9e-13 per term; |term| < 256 and <= 2^14 loci: the sum cannot wrap
   constexpr double FXC = 1024.0;                     // a TAU / MIX term beyond that goes to a coarse companion sum (2^-10, |term| < 2^38)
   auto fx_add = [&](int v, double x, bool coarse)
@@ -767,16 +798,19 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   };
   uint32_t nx = 0;
   unsigned long long gseq = A.seq0;                 // several GPUs: the mailboxes' sequence number
-#define XT(i_) do { if (prof_on) { const long long t1_ = clock64(); wg.prof[8 + i_] += t1_ - xt0; xt0 = t1_; } } while (0)
+#define XT(i_) do { if (prof_on) { const long long t1_ = clock64(); wg.prof[xrow + i_] += t1_ - xt0; xt0 = t1_; } } while (0)
   long long xt0 = 0;
+  // BPA_SMP_DBG & 64, the program-moves kernel: the exchange that follows a real one and adds zeros — nobody is late, so what
+  // it costs is the protocol alone.  It takes its turn with the two sets like any other; its totals go nowhere, its cycles to rows of their own
+  bool xdummy = false; int xrow = 8;
   // one block of <= 15 values (15 sums + the counter = one 128-byte block): the workgroup's sums go to its shard, then its arrival
   // solo (the program-moves kernel): the control wave runs the exchange alone — no workgroup barrier inside
   constexpr bool solo = PROG;
   auto xpush = [&](int v0, int nv)
   {
     const uint32_t par = nx & 1u; ++nx;
-    // 8 shards, a workgroup adds to shard b mod 8: atomics on one word are served one after the other
-    unsigned long long * acc = A.xbuf + (size_t)par*XN + (size_t)(b & 7u)*16u;
+    const XLayout xl = xlayout(A.xshards, b, 0u, 0u);
+    unsigned long long * acc = A.xbuf + (size_t)par*xl.set_words + xl.shard;
     if (tid < (uint32_t)nv)
     {
       const unsigned long long fx = wg.accfx[v0 + (int)tid];
@@ -794,19 +828,30 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
   auto xpoll = [&](int v0, int nv, bool last, bool hold) -> bool
   {
     const uint32_t par = (nx - 1u) & 1u;
-    unsigned long long * set = A.xbuf + (size_t)par*XN;
     if (wv == 0)
     {
       const unsigned long long t_wait = wall_clock64();
-      const unsigned long long prev0 = wg.xprev[par][lane], prev1 = wg.xprev[par][64u + lane];
+      const XLayout xl = xlayout(A.xshards, b, lane, 0u);
+      const unsigned long long * mine = A.xbuf + (size_t)par*xl.set_words + xl.word;
+      const uint32_t step = xlayout(A.xshards, 0u, 0u, 1u).word - xlayout(A.xshards, 0u, 0u, 0u).word, nloads = A.xshards >> 2;     // (the same for every lane)
+      const unsigned long long prev = wg.xprev[par][lane];
       bool ok = true;
-      unsigned long long cur0 = 0, cur1 = 0, d = 0, gd = 0;
+      unsigned long long cur = 0, d = 0, gd = 0;
+      // the workgroup's own arrival is ~1 000 cycles from being readable, and every round of 250 polling waves goes to the lines
+      // the late workgroups' atomics must reach: the first round waits (NOTES §18: 8, 16 and 32 units measured, 16 the fastest)
+      __builtin_amdgcn_s_sleep(XSLEEP_FIRST);
       for (uint32_t rounds = 1;; ++rounds)
       {
-        // TWO loads: lane 16 x + k reads word k of shards x and x + 4; the shards' growth since the set's previous use, added up
-        cur0 = __hip_atomic_load(set + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cur1 = __hip_atomic_load(set + 64u + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        d = (cur0 - prev0) + (cur1 - prev1);
+        // lane 16 x + k reads word k of shards x, x + 4, ...; the shards' growth since the set's previous use, added up
+        // (without a control wave the polling wave holds its loci's state in registers: two loads at a time there, as ever)
+        if constexpr (PROG) cur = nloads == 2u ? xpoll_sum<2>(mine, step) : nloads == 4u ? xpoll_sum<4>(mine, step) : nloads == 8u ? xpoll_sum<8>(mine, step) : xpoll_sum<16>(mine, step);
+        else
+        {
+          cur = 0;
+#pragma unroll 1
+          for (uint32_t j = 0; j < nloads; j += 2u) cur += xpoll_sum<2>(mine + (size_t)j*step, step);
+        }
+        d = cur - prev;
         d += __shfl_xor(d, 16, 64); d += __shfl_xor(d, 32, 64);
         // (test switches, BPA_SMP_INJECT: dbg bit 1024 = every workgroup gives up at its first wait, 2048 = workgroup 0 alone — the
         //  others then run into the real time-out at the next exchange)
@@ -860,11 +905,12 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         }
       }
       XT(3);
-      if (ok)
+      if (ok && xdummy) wg.xprev[par][lane] = cur;
+      else if (ok)
       {
         const unsigned long long dd = A.world > 1 ? gd : d;
         if (lane < (uint32_t)nv) wg.xtot[v0 + (int)lane] = anybad ? __longlong_as_double(0x7ff8000000000000ll) : (double)(long long)dd*(1.0/FX);
-        wg.xprev[par][lane] = cur0; wg.xprev[par][64u + lane] = cur1;
+        wg.xprev[par][lane] = cur;
         // (an unusable term stays flagged through every block of the exchange: its value may lie in a later one)
         if (lane == 0) { if (anybad) wg.xbad_ = 1u; wg.xcoarse_ = anycoarse ? 1u : 0u; if (last) { wg.bad_ = 0; wg.coarse_ = 0; } }
       }
@@ -886,7 +932,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     if (!solo) __syncthreads();                      // every lane's term is in wg.accfx
     XT(0);
     x_nval = nval;
-    if (tid == 0) wg.xbad_ = 0;
+    if (tid == 0 && !xdummy) wg.xbad_ = 0;
     xpush(0, nval < XV ? nval : XV);
   };
   // hold: wave 0 returns from the last block's poll without the closing barrier (and is the only one that may read the
@@ -904,7 +950,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     }
     if (hold || solo)
     {
-      if (wv == 0 && nval > XV && wg.xbad_) { if (lane < (uint32_t)nval) wg.xtot[lane] = __longlong_as_double(0x7ff8000000000000ll); wsync(); }
+      if (wv == 0 && nval > XV && wg.xbad_ && !xdummy) { if (lane < (uint32_t)nval) wg.xtot[lane] = __longlong_as_double(0x7ff8000000000000ll); wsync(); }
       return true;
     }
     if (nval > XV && wg.xbad_)
@@ -1008,6 +1054,16 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
           const bool okx = exchange_end(0, dummy);
           SMP2_TICK(3);
           if (!okx) { aborted = true; __syncthreads(); __syncthreads(); break; }
+          if ((A.dbg & 64u) && A.world == 1)
+          {
+            // (the loci waves stand at B3: wg.accfx is all zeros, and the real exchange's totals and flags stay as they are)
+            xdummy = true; xrow = 16;
+            exchange_begin(base + (mix ? 2 : 5));
+            const bool okd = exchange_end(0, dummy);
+            xdummy = false; xrow = 8;
+            if (!okd) { aborted = true; __syncthreads(); __syncthreads(); break; }
+            if (prof_on) pf_t = clock64();
+          }
           bool accept = false; double lnacc = 0; uint32_t rd_mask = 0;
           if (first)
           {

@@ -345,6 +345,14 @@ unsigned bpa_burnin_schedule(unsigned burnin, unsigned * after, unsigned cap);
    costs finds shortest); the identity is returned instead wherever the simulation does not find the schedule shorter.
    Returns nseg, 0 for arguments out of range (hand_overs > 3 among them).                                               */
 int bpa_sweep_schedule(unsigned lwaves, unsigned steps, double cost_alone, double cost_young, unsigned hand_overs, unsigned char * out);
+/* The layout of the persistent iteration kernel's exchange: the sums of an all-loci step go to one of two accumulator sets; a
+   set is `shards` shards (8, 16, 32 or 64), each one 128-byte line of 16 words (15 sums + the arrival word), one after the
+   other.  A workgroup adds to shard workgroup mod shards; the polling wave's lane
+   16 x + k reads, as its load j (0 .. shards/4 - 1), word k of shard x + 4 j.  out receives 4 numbers, in 8-byte words: the
+   words of one set (the second set follows the first), the words allocated (both sets of the largest layout), and inside a
+   set the offset of the workgroup's shard and of the word that load `load` of lane `lane` reads.
+   Returns the loads a lane makes per round (shards/4), 0 for arguments out of range.                                        */
+int bpa_exchange_layout(unsigned shards, unsigned workgroup, unsigned lane, unsigned load, unsigned * out);
 /* which generator and window the moves draw from (a00_set_proposal_kernel of bpp_amd_host.h; before initialize):
    BPA_KERNEL_UNIFORM (default) our 64-bit streams, window = finetune x (u - 1/2), the acceptance number always drawn;
    BPA_KERNEL_BPP     the reference's own — legacy_rndu (random.c:104-122) and the Bactrian-Laplace variate of
