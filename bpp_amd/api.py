@@ -162,6 +162,10 @@ def lib():
         "bpa_sampler_get_locus_rates": (i, [vp, dp, dp]),
         "bpa_sampler_set_locusrate_moves": (i, [vp, d, d, d, d, d, d]),
         "bpa_sampler_locusrate_counters": (i, [vp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
+        "bpa_sampler_set_heredity": (i, [vp, dp]),
+        "bpa_sampler_get_heredity": (i, [vp, dp]),
+        "bpa_sampler_set_heredity_move": (i, [vp, d, d, d]),
+        "bpa_sampler_heredity_counters": (i, [vp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
         "bpa_sampler_timing": (i, [vp, dp, C.POINTER(C.c_ulong), dp, C.POINTER(C.c_ulong)]),
         "bpa_sampler_work": (i, [vp, dp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
         "bpa_sampler_kind": (i, [vp]),
@@ -210,7 +214,8 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_experimental_build", "bpa_devi
             "bpa_sampler_enable_timing", "bpa_sampler_timing", "bpa_sampler_work", "bpa_sampler_kind", "bpa_sampler_streams", "bpa_sampler_set_p2p", "bpa_sampler_set_proposal_kernel",
             "bpa_sampler_set_program_moves", "bpa_sampler_gibbs_counters",
             "bpa_sampler_set_subst_model", "bpa_sampler_get_subst_model", "bpa_sampler_set_subst_moves",
-            "bpa_sampler_set_locus_rates", "bpa_sampler_get_locus_rates", "bpa_sampler_set_locusrate_moves", "bpa_sampler_locusrate_counters"]
+            "bpa_sampler_set_locus_rates", "bpa_sampler_get_locus_rates", "bpa_sampler_set_locusrate_moves", "bpa_sampler_locusrate_counters",
+            "bpa_sampler_set_heredity", "bpa_sampler_get_heredity", "bpa_sampler_set_heredity_move", "bpa_sampler_heredity_counters"]
 
 
 def _err():
@@ -744,6 +749,30 @@ class Sampler:
         p, a = (C.c_ulong*2)(), (C.c_ulong*2)()
         _chk(lib().bpa_sampler_locusrate_counters(self.h, p, a))
         return dict(mui=(p[0], a[0]), mubar=(p[1], a[1]))
+
+    def set_heredity(self, h):
+        """the loci's heredity scalars h_i (each > 0), before initialize: locus i's population sizes are h_i theta_p in its MSC
+        density; they stay fixed unless set_heredity_move switches the HRDT move on (the generic sampler only)"""
+        h = _f64(h)
+        if len(h) != self.n:
+            raise ValueError("one scalar per locus")
+        _chk(lib().bpa_sampler_set_heredity(self.h, _dp(h)))
+
+    def get_heredity(self):
+        """h_i of every locus"""
+        h = np.ones(self.n)
+        _chk(lib().bpa_sampler_get_heredity(self.h, _dp(h)))
+        return h
+
+    def set_heredity_move(self, ft_h, a=0.0, b=0.0):
+        """BPP's 'heredity = 1 a b': window width of the HRDT move (0: off), h_i ~ gamma(a, b)"""
+        _chk(lib().bpa_sampler_set_heredity_move(self.h, ft_h, a, b))
+
+    def heredity_counters(self):
+        """(proposed, accepted) of the HRDT move (not part of summary()'s totals)"""
+        p, a = C.c_ulong(), C.c_ulong()
+        _chk(lib().bpa_sampler_heredity_counters(self.h, C.byref(p), C.byref(a)))
+        return p.value, a.value
 
     def enable_timing(self, stride=1):
         """HIP events on every stride-th sweep / all-loci launch (0: off)"""

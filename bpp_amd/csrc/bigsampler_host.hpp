@@ -133,7 +133,7 @@ static int gb_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
   const bool mix = q < 0;
   if (!gb_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !gb_eval(s, 1)) return 0;
   hipLaunchKernelGGL(gsm::gdec_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
-                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p);
+                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p, (const double *)nullptr);
   HIPCHK(hipGetLastError());
   s->launches++;
   s->epoch++;
@@ -176,7 +176,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
       for (int p = 0; p < s->sp.npop; ++p)
         if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
       hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                         s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1);
+                         s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)nullptr);
       HIPCHK(hipGetLastError());
       s->logpr_stale = true;
       s->launches += 1;

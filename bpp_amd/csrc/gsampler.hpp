@@ -37,7 +37,8 @@ struct GTree                              // one per locus, in HBM
   uint32_t work_nupd, work_nbr;           // node updates / fresh P-matrices / evaluations of all steps so far (bpa_sampler_work)
   uint32_t work_neval;
   uint32_t pj_gage, pj_gage_acc, pj_gspr, pj_gspr_acc;    // of the proposals / accepted: the gene-node age and the prune-regraft moves (the burn-in's step-length rule wants the move types apart)
-  uint32_t pj_mui, pj_mui_acc, pad_[1];    // the locus's rate move (mode 9): counted apart, NOT part of proposals / accepted (a00_locusrate_counters)
+  uint32_t pj_mui, pj_mui_acc;            // the locus's rate move (mode 9): counted apart, NOT part of proposals / accepted (a00_locusrate_counters)
+  uint32_t pj_hered_acc;                  // acceptances of the heredity-scalar move (mode 10; every locus is proposed once per step: the host counts those)
 };
 static_assert(sizeof(GTree) % 16 == 0, "GTree is copied as uint4");
 
@@ -71,7 +72,8 @@ struct GArgs
   uint32_t i0, iend;                      // the launch's loci [i0, iend) (a half-batch launch; all loci: 0, T)
   uint32_t mode;                          // 0 GAGE k, 1 GSPR k, 2 TAU, 3 MIX, 4 settle (+ THETA statistics), 5 start-up evaluation,
                                           // 6 base frequency k, 7 exchangeability k, 8 alpha (locus.c:2782, 3168; prop_gamma.c:52),
-                                          // 9 the locus's mutation rate mu_i (prop_locusrate_mui, stree.c:9225)
+                                          // 9 the locus's mutation rate mu_i (prop_locusrate_mui, stree.c:9225),
+                                          // 10 the locus's heredity scalar (prop_heredity, gtree.c:8214; gstep2_kernel only: decided in the launch)
   uint32_t k;
   uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch),
                                           // 3 commit (start-up), 4 per-locus decisions of a substitution-parameter step
@@ -81,6 +83,11 @@ struct GArgs
   double * mui, * mui_old;                // [T] the rates; [T] a pending mode-9 step's old values
   const struct GLrState * lr;             // the rates' mean mu_bar (mode 9 reads it)
   double ft_mui, a_mui;
+  // heredity scalars (bpa_sampler_set_heredity): population p's term of locus i's MSC density is taken at h_i theta_p
+  // (gtree.c:3938-3943).  hered == null: none was ever set and the move is off, every h_i is 1 and no load is made; a locus whose
+  // h_i is exactly 1.0 takes the table's log(2/theta) as before
+  double * hered;                         // [T]
+  double ft_h, h_a, h_b;                  // mode 10 (HRDT): window width, the gamma(a, b) prior
   double * sm, * sm_old;                  // [T][11] freqs | exchangeabilities | alpha of every locus; [T][2] the pending step's old values
   double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
   const double * lnl_new;                 // [T] lnL of the pending step's evaluation (task = locus)
@@ -126,7 +133,7 @@ __device__ __forceinline__ bool g_accept(a00_rng_t & r, const uint32_t bpp, cons
 }
 
 // the MSC density term of population p from the lane's own state (density_term of sampler.hpp, ages in S.time)
-__device__ __forceinline__ double gdensity_term(const GState & S, const Species & sp, const double * tau, int p, double & T2h_out)
+__device__ __forceinline__ double gdensity_term(const GState & S, const Species & sp, const double * tau, int p, double & T2h_out, const double h)
 {
   uint32_t nodes = S.pnodes[p];
   const int ncoal = S.nc_new[p], nin = S.nin_new[p];
@@ -148,8 +155,18 @@ __device__ __forceinline__ double gdensity_term(const GState & S, const Species 
     prev = tk;
   }
   double c = 0;
-  if (ncoal) c += ncoal*tau[2*MAXPOP + p];
-  if (T2h) c -= T2h/(tau[MAXPOP + p]*1.0);
+  if (h == 1.0)
+  {
+    if (ncoal) c += ncoal*tau[2*MAXPOP + p];
+    if (T2h) c -= T2h/(tau[MAXPOP + p]*1.0);
+  }
+  else
+  {
+    // the locus's heredity scalar: h theta first, its logarithm in place (tree_logpr_stats of a00_driver.c)
+    const double thh = h*tau[MAXPOP + p];
+    if (ncoal) c += ncoal*log(2.0/thh);
+    if (T2h) c -= T2h/thh;
+  }
   T2h_out = T2h;
   return c;
 }
@@ -157,14 +174,14 @@ __device__ __forceinline__ double gdensity_term(const GState & S, const Species 
 // the whole density, populations in order (tree_logpr of a00_driver.c); optionally leaves the THETA statistics
 template <int TT>
 __device__ double gdensity(GState & S, const LTree<TT> & T, LCounts & cn, const LSpecies & sp, const Species & spl, const double * tau,
-                           int8_t * nc_out, double * t2h_out, uint32_t stride)
+                           int8_t * nc_out, double * t2h_out, uint32_t stride, const double h)
 {
   smp::density_prepare<TT>(S, T, cn, sp, (1u << sp.npop) - 1u);
   double logpr = 0;
   for (int p = 0; p < sp.npop; ++p)
   {
     double t2h;
-    logpr += gdensity_term(S, spl, tau, p, t2h);
+    logpr += gdensity_term(S, spl, tau, p, t2h, h);
     if (nc_out) { nc_out[(size_t)p*stride] = S.nc_new[p]; t2h_out[(size_t)p*stride] = t2h; }
   }
   return logpr;
@@ -228,6 +245,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
   double lnl_cur = 0, logpr_cur = 0;
   uint32_t nprop = 0, nacc = 0, w_nupd = 0, w_nbr = 0, w_nev = 0;
   GLocus L{};
+  const double hered = (valid && A.hered) ? A.hered[i] : 1.0;         // the locus's heredity scalar (no step of this kernel moves it)
   if (valid)
   {
     GTree & g = A.trees[i];
@@ -307,7 +325,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
     }
   }
   // ---- 2. THETA moved the thetas since this density was stored
-  if (valid && A.refresh_logpr) logpr_cur = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0);
+  if (valid && A.refresh_logpr) logpr_cur = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0, hered);
   __syncthreads();
 
   // ---- 3. the proposed species tree of an all-loci step is this workgroup's copy of the taus
@@ -360,7 +378,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
         if (T.parent[k] >= 0) brm |= 1u << k;
         ndm |= smp::path_mask(T, k);
       }
-      const double lp_new = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0);
+      const double lp_new = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0, hered);
       A.logpr_new[i] = lp_new;
       A.delta[i] = ((lp_new - logpr_cur) + below*lminf) + above*lmaxf;          // p_delta of the host driver
       A.lnl_cur[i] = lnl_cur;
@@ -432,7 +450,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
         for (uint32_t m = brm; m; m &= m - 1) smp::swap_pmat(T, __ffs(m) - 1);       // start-up evaluates in place:
         for (uint32_t m = ndm; m; m &= m - 1) smp::swap_clv(T, __ffs(m) - 1);        // toggle twice = no toggle
       }
-      const double lp_new = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0);
+      const double lp_new = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0, hered);
       A.logpr_new[i] = lp_new;
       A.delta[i] = (lp_new - logpr_cur) + (double)ninner*A.mix_lnc;
       A.lnl_cur[i] = lnl_cur;
@@ -440,7 +458,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
     }
     if (ok && MODE <= 1)
     {
-      A.logpr_new[i] = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0);
+      A.logpr_new[i] = gdensity(S, T, cn, sp, spl, s_tau, nullptr, nullptr, 0, hered);
       A.hast[i] = hast;
     }
     if (ok && MODE != 5) { w_nupd += (uint32_t)S.nops; w_nbr += (uint32_t)__popc(S.brm); ++w_nev; }
@@ -544,7 +562,7 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
   }
 
   // ---- 6. mode 4: the sufficient statistics of the settled state, for the THETA kernel
-  if (valid && MODE == 4) (void)gdensity(S, T, cn, sp, spl, s_tau, A.pop_nc + i, A.pop_t2h + i, A.T);
+  if (valid && MODE == 4) (void)gdensity(S, T, cn, sp, spl, s_tau, A.pop_nc + i, A.pop_t2h + i, A.T, hered);
 
   // ---- 7. store
   if (valid)
@@ -628,7 +646,7 @@ constexpr int GPROG_FLAG0 = 3*MAXPOP;          // the sum kernels' output block:
 __global__ void __launch_bounds__(1024) gprog_sums_kernel(const double * __restrict__ lnl_cur, const double * __restrict__ lnl_new,
                                                           const double * __restrict__ delta, const uint8_t * __restrict__ active,
                                                           const double * __restrict__ t2h3, uint32_t T, int with_t2h, double * out,
-                                                          unsigned long long seq)
+                                                          unsigned long long seq, const double * __restrict__ hered)
 {
   __shared__ double sh[1024];
   __shared__ long long shl[3][1024];
@@ -640,7 +658,7 @@ __global__ void __launch_bounds__(1024) gprog_sums_kernel(const double * __restr
     if (with_t2h)
       for (int j = 0; j < 3; ++j)
       {
-        const double x = t2h3[(size_t)3*i + j];
+        const double x = hered ? t2h3[(size_t)3*i + j]/hered[i] : t2h3[(size_t)3*i + j];      // C2ji/heredity, then the fixed point (stree.c:5888)
         if (!(fabs(x) < 256.0)) bad = 1; else c[j] += llrint(x*1099511627776.0);
       }
   }
@@ -664,9 +682,10 @@ __global__ void __launch_bounds__(1024) gprog_sums_kernel(const double * __restr
   if (seq) { __threadfence_system(); __hip_atomic_store(reinterpret_cast<unsigned long long *>(out) + GPROG_FLAG0, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 }
 
-// THETA: per population the coalescences and the T2h over all loci (theta_sums of a00_driver.c: integers, no order)
+// THETA: per population the coalescences and the T2h/h_i over all loci (theta_sums of a00_driver.c: integers, no order)
 __global__ void __launch_bounds__(1024) gprog_theta_sums_kernel(const int8_t * __restrict__ pop_nc, const double * __restrict__ pop_t2h,
-                                                                uint32_t T, uint32_t onmask, long long * out, unsigned long long seq)
+                                                                uint32_t T, uint32_t onmask, long long * out, unsigned long long seq,
+                                                                const double * __restrict__ hered)
 {
   __shared__ long long shk[1024], sht[1024];
   __shared__ int shb[1024];
@@ -675,7 +694,7 @@ __global__ void __launch_bounds__(1024) gprog_theta_sums_kernel(const int8_t * _
   if ((onmask >> p) & 1u)
     for (uint32_t i = threadIdx.x; i < T; i += 1024)
     {
-      const double x = pop_t2h[(size_t)p*T + i];
+      const double x = hered ? pop_t2h[(size_t)p*T + i]/hered[i] : pop_t2h[(size_t)p*T + i];      // (stree.c:3679)
       if (!(fabs(x) < 256.0)) bad = 1; else { k += pop_nc[(size_t)p*T + i]; t += llrint(x*1099511627776.0); }
     }
   shk[threadIdx.x] = k; sht[threadIdx.x] = t; shb[threadIdx.x] = bad;
@@ -738,7 +757,8 @@ __device__ __forceinline__ long long gdec_join64(double hi, double lo) { return 
 // gprog_sums_kernel / gprog_theta_sums_kernel with their results as doubles in a device buffer
 __global__ void __launch_bounds__(1024) gdec_sums_kernel(const double * __restrict__ lnl_cur, const double * __restrict__ lnl_new,
                                                          const double * __restrict__ delta, const uint8_t * __restrict__ active,
-                                                         const double * __restrict__ t2h3, uint32_t T, int with_t2h, double * out)
+                                                         const double * __restrict__ t2h3, uint32_t T, int with_t2h, double * out,
+                                                         const double * __restrict__ hered)
 {
   __shared__ double sh[1024];
   __shared__ long long shl[3][1024];
@@ -750,7 +770,7 @@ __global__ void __launch_bounds__(1024) gdec_sums_kernel(const double * __restri
     if (with_t2h)
       for (int j = 0; j < 3; ++j)
       {
-        const double x = t2h3[(size_t)3*i + j];
+        const double x = hered ? t2h3[(size_t)3*i + j]/hered[i] : t2h3[(size_t)3*i + j];      // C2ji/heredity, then the fixed point (stree.c:5888)
         if (!(fabs(x) < 256.0)) bad = 1; else c[j] += llrint(x*1099511627776.0);
       }
   }
@@ -775,7 +795,7 @@ __global__ void __launch_bounds__(1024) gdec_sums_kernel(const double * __restri
 }
 
 __global__ void __launch_bounds__(1024) gdec_theta_sums_kernel(const int8_t * __restrict__ pop_nc, const double * __restrict__ pop_t2h,
-                                                               uint32_t T, uint32_t onmask, double * out)
+                                                               uint32_t T, uint32_t onmask, double * out, const double * __restrict__ hered)
 {
   __shared__ long long shk[1024], sht[1024];
   __shared__ int shb[1024];
@@ -784,7 +804,7 @@ __global__ void __launch_bounds__(1024) gdec_theta_sums_kernel(const int8_t * __
   if ((onmask >> p) & 1u)
     for (uint32_t i = threadIdx.x; i < T; i += 1024)
     {
-      const double x = pop_t2h[(size_t)p*T + i];
+      const double x = hered ? pop_t2h[(size_t)p*T + i]/hered[i] : pop_t2h[(size_t)p*T + i];      // (stree.c:3679)
       if (!(fabs(x) < 256.0)) bad = 1; else { k += pop_nc[(size_t)p*T + i]; t += llrint(x*1099511627776.0); }
     }
   shk[threadIdx.x] = k; sht[threadIdx.x] = t; shb[threadIdx.x] = bad;

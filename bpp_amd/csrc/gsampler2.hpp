@@ -42,7 +42,7 @@ template <int NT> struct Step2LDS
 template <uint32_t MODE, int NT, bool WAVE_ONLY, bool BPP = false>
 __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl & C, Step2LDS<NT> & SH, const uint32_t lane, const uint32_t i, const bool valid)
 {
-  static_assert(MODE <= 3, "GAGE, GSPR, TAU, MIX");
+  static_assert(MODE <= 3 || MODE == 10, "GAGE, GSPR, TAU, MIX, HRDT");
   using Cf = smp2::Cfg<NT>;
   constexpr int G = Cf::G, NN = Cf::NN, W = Cf::W;
   LocLDS<NT> * s_loc = SH.loc;
@@ -85,6 +85,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
   smp2::Stream<BPP> rng{g.rng};                                // (BPP: the reference's generator, Bactrian-Laplace windows, its acceptance rule)
   double lnl_cur = g.lnl, logpr_cur = g.logpr;
   uint32_t nprop = g.proposals, nacc = g.accepted, w_nupd = g.work_nupd, w_nbr = g.work_nbr, w_nev = g.work_neval, pj_gage = g.pj_gage, pj_gage_acc = g.pj_gage_acc, pj_gspr = g.pj_gspr, pj_gspr_acc = g.pj_gspr_acc;
+  uint32_t pj_hered_acc = MODE == 10 ? g.pj_hered_acc : 0u;
   const gsm::GLocus L = A.loc[ic];
   const int gl_i = li < MAXPOP ? (int)L.gl[li] : 0;
   const uint32_t d_active = A.active[ic], d_flag = *A.flag;
@@ -97,6 +98,8 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
   const double mui_r = A.mui ? A.mui[ic] : 1.0;
   const double mui_o = (A.mui && C.pend == 4 && A.pend_mode == 9) ? A.mui_old[ic] : mui_r;
   double rate_mui = mui_r;
+  // the locus's heredity scalar (null: none was ever set, 1 without a load)
+  const double hered_r = A.hered ? A.hered[ic] : 1.0;
 
   if (lane < (uint32_t)(3*MAXPOP)) s_tau[lane] = tau_r;
   if (lane < 16u) s_anc[lane] = lane < (uint32_t)MAXPOP ? (uint32_t)SP.anc[lane] : 0u;
@@ -120,6 +123,10 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
     pl.tau = s_tau[lp]; pl.theta = s_tau[MAXPOP + lp]; pl.l2t = s_tau[2*MAXPOP + lp];
     pl.ptau = pl.parent >= 0 ? s_tau[pl.parent] : -1.0;
   }
+  // a locus with a heredity scalar other than 1: the lane's population at h theta, its logarithm once, here — density_term stays
+  // as it is (tree_logpr_stats of a00_driver.c: h theta first, gtree.c:3938-3943)
+  const double theta_p = pl.theta;
+  if (hered_r != 1.0) { pl.theta = hered_r*theta_p; pl.l2t = log(2.0/pl.theta); }
   LocLDS<NT> & S = s_loc[slot];
   // fuse_pm (step 4 fills the fresh branches' P-matrices): what that needs of the locus is asked for NOW and arrives while
   // the proposal is made — the lane's category rate, the matrix index, the first matrix's parameter block (dealt over the
@@ -302,6 +309,30 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
       ok = MODE == 0 ? smp2::propose_gage<NT, BPP>(T, rng, S.time, (int)C.k, pl, s_anc, s_tau, SP.ft_gage, li, gbase, pr)
                      : smp2::propose_gspr<NT, BPP>(T, rng, S.time, (int)C.k, pl, gl_i, s_anc, s_tau, s_lograt, SP.ft_gspr, li, gbase, pr);
   }
+  else if (MODE == 10)
+  {
+    // HRDT (hered_step of a00_driver.c; prop_heredity, gtree.c:8214): h' = |h + ft_h w|, the gamma(a, b) prior's ratio, the
+    // locus's density at h' against the stored one — from the counts and the T2h density_term has just left for the current tree
+    // (neither depends on h).  No likelihood work: decided here, nothing is left pending
+    if (valid)
+    {
+      const double h_new = fabs(hered_r + A.ft_h*rng.window());
+      if (!(h_new > 0) || !(h_new < __longlong_as_double(0x7ff0000000000000ll))) rng.skip();
+      else
+      {
+        const double thh = h_new*theta_p;
+        double c = 0;
+        if (mync) c += mync*log(2.0/thh);
+        if (my_t2h) c -= my_t2h/thh;
+        if (li < npop) S.contrib_new[li] = c;
+        smp2::wsync();
+        double lp = 0;
+        for (int p = 0; p < npop; ++p) lp += S.contrib_new[p];
+        const double lnacc = ((A.h_a - 1)*log(h_new/hered_r) - A.h_b*(h_new - hered_r)) + (lp - logpr_cur);
+        if (rng.accept(lnacc)) { logpr_cur = lp; ++pj_hered_acc; if (li == 0) A.hered[i] = h_new; }
+      }
+    }
+  }
   else if (valid)
   {
     // an all-loci step (sweep2.hpp's step_locus): the proposed species tree in the lanes' registers, every population's term
@@ -345,7 +376,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
   Op opw[NT - 1]; int nops = 0;
   for (int k = 0; k < NT - 1; ++k) opw[k] = 0;
   double lp_new = logpr_cur;
-  if (ok || (MODE >= 2 && valid))
+  if (ok || ((MODE == 2 || MODE == 3) && valid))
   {
     smp2::wsync();
     density_counts();
@@ -388,7 +419,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
   if (valid && li == 0)
   {
     if (MODE <= 1) { if (ok) { A.logpr_new[i] = lp_new; A.hast[i] = pr.hast; } }
-    else
+    else if (MODE != 10)
     {
       A.logpr_new[i] = lp_new;
       // p_delta of the host driver; the program's moves (A.prog): the densities' change over all loci follows from the sums of
@@ -521,6 +552,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
     {
       g.rng = rng.r; g.root = T.root; g.lnl = lnl_cur; g.logpr = logpr_cur; g.proposals = nprop; g.accepted = nacc;
       g.work_nupd = w_nupd; g.work_nbr = w_nbr; g.work_neval = w_nev; g.pj_gage = pj_gage; g.pj_gage_acc = pj_gage_acc; g.pj_gspr = pj_gspr; g.pj_gspr_acc = pj_gspr_acc;
+      if (MODE == 10) g.pj_hered_acc = pj_hered_acc;
     }
   }
   if (WAVE_ONLY) smp2::wsync();                  // (the next step of a chain reuses the LDS block)
@@ -537,7 +569,7 @@ __global__ void __launch_bounds__(64) gstep2_kernel(const gsm::GArgs A)
   __shared__ Step2LDS<NT> SH;
   constexpr uint32_t LPW = (uint32_t)smp2::Cfg<NT>::LPW, G = (uint32_t)smp2::Cfg<NT>::G;
   const uint32_t i = A.i0 + blockIdx.x*LPW + threadIdx.x/G;
-  const StepCtl C{MODE >= 2 ? A.tau_q : A.k, A.pend, A.refresh_logpr, A.fmt20, A.pend_mode};
+  const StepCtl C{(MODE == 2 || MODE == 3) ? A.tau_q : A.k, A.pend, A.refresh_logpr, A.fmt20, A.pend_mode};
   gstep2_body<MODE, NT, false, BPP>(A, C, SH, threadIdx.x, i, i < A.iend);
 }
 

@@ -49,6 +49,20 @@ static void gs_lr_args(const bpa_sampler * s, gsm::GArgs & a)
   a.mui = s->g_mui.p; a.mui_old = s->g_mui_old.p; a.lr = s->g_lr.p; a.ft_mui = s->g_lr_ft[0]; a.a_mui = s->g_a_mui;
 }
 
+// the heredity scalars' device array: made when scalars were set or the HRDT move is on — a sampler that never heard of them
+// passes a null pointer, which its kernels read as "every scalar 1" without a load
+static int gs_hered_ready(bpa_sampler * s)
+{
+  if (s->g_hered.p || (s->g_hered_host.empty() && !(s->g_h_ft > 0))) return 1;
+  const unsigned T = s->nloci;
+  if (s->g_hered_host.size() != T) s->g_hered_host.assign(T, 1.0);
+  return upload(s->g_hered, s->g_hered_host.data(), T) ? 1 : 0;
+}
+static void gs_hered_args(const bpa_sampler * s, gsm::GArgs & a)
+{
+  a.hered = s->g_hered.p; a.ft_h = s->g_h_ft; a.h_a = s->g_h_a; a.h_b = s->g_h_b;
+}
+
 // K6 for every locus of the sampler from the values now in its parameter block (pll_update_eigen, locus.c:2462-2476)
 static int gs_refresh_eigen(bpa_sampler * s)
 {
@@ -193,6 +207,8 @@ static int gs_upload(bpa_sampler * s)
   if (!gs_subst_ready(s)) return 0;
   s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free();
   if (!gs_lr_ready(s)) return 0;
+  s->g_hered.free();
+  if (!gs_hered_ready(s)) return 0;
   // every slot starts as "not part of the step", every matrix entry as a hole
   HIPCHK(hipMemsetAsync(s->g_recs.p, 0xff, nrec*sizeof(uint4), e->stream));
   HIPCHK(hipMemsetAsync(s->g_mat2.p, 0xff, nmat*sizeof(MatRec2), e->stream));
@@ -328,20 +344,23 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   a.bpp = s->kernel_bpp ? 1u : 0u; a.prog = gs_prog(s) ? 1u : 0u; a.t2h3 = s->g_t2h3.p; a.tau_w = tau_w;
   a.slot_tab = e->d_slot_tab.p;
   gs_lr_args(s, a);
+  gs_hered_args(s, a);
   if (mode == 9 && !a.mui) return fail("bpa_sampler: a rate step without the rates' arrays");
+  if (mode == 10 && !a.hered) return fail("bpa_sampler: a heredity step without the scalars' array");
   a.dstep = (s->gp_dev && (mode == 2 || mode == 3)) ? s->g_dst.p : nullptr;
   // a frequency / exchangeability step — proposed now, or rolled back now for the loci that rejected it — leaves
   // parameter blocks whose eigensystems are stale: refreshed before the next evaluation (gs_eval)
   // ... unless the launch is the one-lane kernel (settle, start-up, the parameter moves) on 4-state loci whose eigensystems are
   // level now: its lanes then refresh what they write themselves (GArgs::fuse_eigen, round 6) and nothing is left stale
   const bool touches_eigen = mode == 6 || mode == 7 || (s->g_pend == 4 && (s->g_pend_mode == 6 || s->g_pend_mode == 7));
-  a.fuse_eigen = (touches_eigen && mode >= 4 && !s->g_s20 && !s->g_alljc && e->usedata && !s->g_eigen_dirty && !s->env_noeigfuse) ? 1u : 0u;
+  a.fuse_eigen = (touches_eigen && mode >= 4 && mode != 10 && !s->g_s20 && !s->g_alljc && e->usedata && !s->g_eigen_dirty && !s->env_noeigfuse) ? 1u : 0u;
   if (touches_eigen && !a.fuse_eigen) s->g_eigen_dirty = true;
   // diagnostics (BPA_GS_DIFF=1): a GAGE / GSPR step by both kernels from the same state, whatever differs is reported;
   // the run goes on with the one-lane kernel's result
 #define GS2_CASES(NT_, BPP_, GRID_, ST_) switch (a.mode) { \
       case 0: hipLaunchKernelGGL((gsm2::gstep2_kernel<0, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; case 1: hipLaunchKernelGGL((gsm2::gstep2_kernel<1, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; \
-      case 2: hipLaunchKernelGGL((gsm2::gstep2_kernel<2, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; default: hipLaunchKernelGGL((gsm2::gstep2_kernel<3, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; }
+      case 2: hipLaunchKernelGGL((gsm2::gstep2_kernel<2, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; case 10: hipLaunchKernelGGL((gsm2::gstep2_kernel<10, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; \
+      default: hipLaunchKernelGGL((gsm2::gstep2_kernel<3, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; }
 #define GS2_LAUNCH(GRID_, ST_) do { \
     if (s->kernel_bpp) { if (s->maxtips <= 8) GS2_CASES(8, true, GRID_, ST_) else GS2_CASES(16, true, GRID_, ST_) } \
     else               { if (s->maxtips <= 8) GS2_CASES(8, false, GRID_, ST_) else GS2_CASES(16, false, GRID_, ST_) } } while (0)
@@ -467,8 +486,9 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
     a.i0 = s->g_forked ? s->g_pi[h] : 0u; a.iend = s->g_forked ? s->g_pi[h + 1] : s->nloci;
     const dim3 grid((a.iend - a.i0 + gsm::GBS - 1)/gsm::GBS), block(gsm::GBS);
     hipStream_t st = h ? s->g_st[h] : e->stream;
-    // GAGE / GSPR / TAU / MIX: a group of lanes per locus (gsampler2.hpp; BPA_GS_V1=1: the one-lane-per-locus kernel)
-    if (a.mode <= 3 && !gs_v1)
+    // GAGE / GSPR / TAU / MIX: a group of lanes per locus (gsampler2.hpp; BPA_GS_V1=1: the one-lane-per-locus kernel); HRDT has
+    // the lane-group form only
+    if ((a.mode <= 3 && !gs_v1) || a.mode == 10)
     {
       const unsigned lpw = s->maxtips <= 8 ? 4u : 2u;
       GS2_LAUNCH(dim3((a.iend - a.i0 + lpw - 1)/lpw), st);
@@ -507,7 +527,7 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
     fprintf(stderr, "  first start -> last end %.2f us\n", (t1 - t0)*0.01);
   }
 #endif
-  s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : mode >= 6 ? 4u : 0u;
+  s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : (mode >= 6 && mode != 10) ? 4u : 0u;      // (HRDT decides in its own launch)
   s->g_pend_mode = mode; s->g_pend_k = k;
   return 1;
 }
@@ -717,6 +737,7 @@ static int gs_chain(bpa_sampler * s)
   a.pend_mode = s->g_pend_mode; a.pend_k = s->g_pend_k; a.sm = s->g_sm.p; a.sm_old = s->g_sm_old.p;
   a.bpp = s->kernel_bpp ? 1u : 0u; a.prog = gs_prog(s) ? 1u : 0u; a.t2h3 = s->g_t2h3.p;
   gs_lr_args(s, a);
+  gs_hered_args(s, a);
   a.fmt20 = 1u; a.maxops20 = s->g_maxops;
   a.ops20 = s->g_ops20.p; a.op_rng20 = s->g_oprng.p; a.root20 = s->g_root20.p; a.mat_task20 = s->g_mtask.p; a.mat_pm20 = s->g_mpm.p;
   a.i0 = 0; a.iend = s->nloci;
@@ -929,7 +950,7 @@ static int gs_prog_theta(bpa_sampler * s)
   unsigned long long pseq = 0;
   double * pout = gs_prog_out(s, &pseq);
   hipLaunchKernelGGL(gsm::gprog_theta_sums_kernel, dim3(npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p, s->nloci, onmask,
-                     reinterpret_cast<long long *>(pout), pseq);
+                     reinterpret_cast<long long *>(pout), pseq, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   if (!gs_prog_fetch(s, pout, h, (size_t)3*npop*sizeof(long long), pseq, npop)) return 0;
   if (s->allreduce)
@@ -996,7 +1017,7 @@ static int gs_prog_tau(bpa_sampler * s, int q)
   unsigned long long pseq = 0;
   double * pout = gs_prog_out(s, &pseq);
   hipLaunchKernelGGL(gsm::gprog_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
-                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, 1, pout, pseq);
+                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, 1, pout, pseq, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   if (!gs_prog_fetch(s, pout, out, 5*sizeof(double), pseq, 1)) return 0;
   s->launches++;
@@ -1083,7 +1104,7 @@ static int gs_prog_mix(bpa_sampler * s)
   unsigned long long pseq = 0;
   double * pout = gs_prog_out(s, &pseq);
   hipLaunchKernelGGL(gsm::gprog_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
-                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, 0, pout, pseq);
+                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, 0, pout, pseq, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   if (!gs_prog_fetch(s, pout, out, 5*sizeof(double), pseq, 1)) return 0;
   s->launches++;
@@ -1145,7 +1166,7 @@ static int gs_dec_launch(bpa_sampler * s, int q, int next)
 static int gs_dev_theta(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
-  hipLaunchKernelGGL(gsm::gdec_theta_sums_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p, s->nloci, gs_theta_mask(s), s->g_dsum.p);
+  hipLaunchKernelGGL(gsm::gdec_theta_sums_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p, s->nloci, gs_theta_mask(s), s->g_dsum.p, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   s->launches++;
   s->logpr_stale = true;
@@ -1158,7 +1179,7 @@ static int gs_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
   const bool mix = q < 0;
   if (!gs_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !gs_eval(s, 1)) return 0;
   hipLaunchKernelGGL(gsm::gdec_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
-                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p);
+                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   s->launches++;
   s->epoch++;
@@ -1212,6 +1233,8 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
   if (!gs_subst_ready(s)) return 0;
   if (gs_lr_moves(s) && !(s->g_a_mui > 0)) return fail("bpa_sampler: the locus-rate moves need a_mui > 0");
   if (!gs_lr_ready(s)) return 0;
+  if (s->g_h_ft > 0 && !(s->g_h_a > 0 && s->g_h_b > 0)) return fail("bpa_sampler: the heredity move needs a, b > 0");
+  if (!gs_hered_ready(s)) return 0;
   s->host_current = false;
   const bool prog = gs_prog(s);
   if (s->kernel_bpp && !prog) return fail("bpa_sampler: on a generic sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
@@ -1267,18 +1290,18 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
         if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
       if (!s->allreduce)
         hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1);
+                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)s->g_hered.p);
       else
       {
         hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0);
+                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0, (const double *)s->g_hered.p);
         double * ar = s->sum_ext ? s->sum_ext : s->theta_sums.p;
         const size_t nb = (size_t)s->sp.npop*sizeof(double);
         if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(ar, s->theta_sums.p, nb, hipMemcpyDeviceToDevice, e->stream));
         if (!s->allreduce(s->allreduce_ctx, ar, (unsigned)s->sp.npop, (void *)e->stream)) return fail("bpa_sampler: the all-reduce callback failed");
         if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(s->theta_sums.p, ar, nb, hipMemcpyDeviceToDevice, e->stream));
         hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1);
+                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1, (const double *)s->g_hered.p);
       }
       HIPCHK(hipGetLastError());
       s->logpr_stale = true;
@@ -1293,6 +1316,9 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
     const double uacc = a00_rndu(&s->grng);
     if (!gs_step(s, 3, 0, 0.0, c, lnc) || !gs_eval(s, 1) || !gs_decide(s, uacc, -1, 0.0, c, lnc)) return 0;
     }
+    // the heredity scalars after MIX, before the substitution parameters (method.c:5616-5621; hered_step of a00_driver.c): one
+    // launch per part-batch that settles MIX, proposes and decides — no evaluation, nothing pending afterwards
+    if (s->g_h_ft > 0) { if (!gs_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
     // the substitution-parameter moves come last (method.c:5699-5735; param_step of a00_driver.c)
     if (s->g_ft[0] > 0) for (unsigned j = 0; j < 3; ++j)  { if (!gs_step(s, 6, j) || !gs_eval(s, 0)) return 0; }
     if (s->g_ft[1] > 0) for (unsigned j = 0; j < 6; ++j)  { if (j != 1 && (!gs_step(s, 7, j) || !gs_eval(s, 0))) return 0; }
@@ -1337,6 +1363,7 @@ static int gs_download(bpa_sampler * s)
     HIPCHK(hipMemcpyAsync(s->g_mui_host.data(), s->g_mui.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipMemcpyAsync(&s->g_lr_host, s->g_lr.p, sizeof(gsm::GLrState), hipMemcpyDeviceToHost, e->stream));
   }
+  if (s->g_hered.p) HIPCHK(hipMemcpyAsync(s->g_hered_host.data(), s->g_hered.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 1;
 }
@@ -1441,5 +1468,63 @@ extern "C" int bpa_sampler_locusrate_counters(bpa_sampler_t * s, unsigned long p
   for (const auto & t : s->g_trees) { p += t.pj_mui; a += t.pj_mui_acc; }
   if (prop) { prop[0] = p; prop[1] = (unsigned long)s->g_lr_host.nprop; }
   if (acc) { acc[0] = a; acc[1] = (unsigned long)s->g_lr_host.nacc; }
+  return 1;
+}
+
+// ---- heredity scalars (include/bpp_amd.h): the generic sampler's; every other kind refuses them
+static int hered_refuse(const bpa_sampler * s, const char * who)
+{
+  const char * kind = s->comp ? "composite" : s->big ? "big-tree" : "persistent / sweep";
+  if (!s->comp && s->generic) return 1;
+  static thread_local std::string msg;
+  msg = std::string(who) + ": heredity scalars and their move run on the generic sampler only (this one is the " + kind +
+        " sampler); BPA_SMP_GENERIC=1 makes the generic sampler take loci the LDS kernels would otherwise";
+  return fail(msg.c_str());
+}
+
+extern "C" int bpa_sampler_set_heredity(bpa_sampler_t * s, const double * h)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!hered_refuse(s, "bpa_sampler_set_heredity")) return 0;
+  if (!h) return fail("bpa_sampler_set_heredity: null argument");
+  for (unsigned i = 0; i < s->nloci; ++i)
+    if (!(h[i] > 0) || !std::isfinite(h[i])) return fail("bpa_sampler_set_heredity: every scalar is > 0 and finite");
+  if (s->uploaded)
+    return fail("bpa_sampler_set_heredity: the sampler is running — set the loci's scalars before bpa_sampler_initialize");
+  s->g_hered_host.assign(h, h + s->nloci);
+  return 1;
+}
+
+extern "C" int bpa_sampler_get_heredity(bpa_sampler_t * s, double * h)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!hered_refuse(s, "bpa_sampler_get_heredity")) return 0;
+  if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
+  if (h) for (unsigned i = 0; i < s->nloci; ++i) h[i] = s->g_hered_host.size() == s->nloci ? s->g_hered_host[i] : 1.0;
+  return 1;
+}
+
+extern "C" int bpa_sampler_set_heredity_move(bpa_sampler_t * s, double ft_h, double a, double b)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if ((s->comp || !s->generic) && ft_h == 0) return 1;        // (nothing asked for)
+  if (!hered_refuse(s, "bpa_sampler_set_heredity_move")) return 0;
+  if (!(ft_h >= 0) || !std::isfinite(ft_h)) return fail("bpa_sampler_set_heredity_move: the width is >= 0 and finite");
+  if (ft_h > 0 && (!(a > 0) || !(b > 0) || !std::isfinite(a) || !std::isfinite(b)))
+    return fail("bpa_sampler_set_heredity_move: a, b > 0 and finite while the move is on");
+  // (width and prior travel with every launch; the scalars' array is made at the next iterate if there is none yet)
+  s->g_h_ft = ft_h; s->g_h_a = a; s->g_h_b = b;
+  return 1;
+}
+
+extern "C" int bpa_sampler_heredity_counters(bpa_sampler_t * s, unsigned long * proposed, unsigned long * accepted)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!hered_refuse(s, "bpa_sampler_heredity_counters")) return 0;
+  if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
+  unsigned long a = 0;
+  for (const auto & t : s->g_trees) a += t.pj_hered_acc;
+  if (proposed) *proposed = s->g_h_prop;
+  if (accepted) *accepted = a;
   return 1;
 }

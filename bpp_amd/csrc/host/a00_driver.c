@@ -72,6 +72,10 @@ struct a00_driver
   double * mui, * mui_old;              /* what a00_set_locus_rates left (a tree set afterwards starts from it); a pending MUI step's old values */
   double ft_mui, ft_mubar, a_mui, a_mubar, b_mubar, mubar;
   unsigned long lr_prop[2], lr_acc[2];  /* 0: MUI, 1: MUBAR — apart from proposals / accepted */
+  /* heredity scalars (a00_set_heredity / a00_set_heredity_move): h_i multiplies every theta in locus i's MSC density */
+  double * hered;                       /* [nloci]; NULL when never set: every h_i is 1 and nothing of a trajectory changes */
+  double ft_h, h_a, h_b;
+  unsigned long h_prop, h_acc;          /* HRDT — apart from proposals / accepted */
   int initialized;
   /* per-locus staging of a step (a00_set_threads): the loci of a step are proposed in parallel — every draw of a
      per-locus proposal comes from that locus's own stream, so the trajectory does not depend on the thread count —
@@ -226,7 +230,7 @@ void a00_destroy(a00_driver_t * d)
   }
   d->view[d->cur_view].s_br = d->s_br; d->view[d->cur_view].s_nd = d->s_nd;
   { int v; for (v = 0; v < 3; ++v) { free(d->view[v].s_br); free(d->view[v].s_nd); } }
-  free(d->rng); free(d->zrng); free(d->sm); free(d->sm_ncat); free(d->sm_old); free(d->mui); free(d->mui_old); free(d->trees); free(d->b_locus); free(d->b_tree); free(d->b_br_off); free(d->b_nd_off);
+  free(d->rng); free(d->zrng); free(d->sm); free(d->sm_ncat); free(d->sm_old); free(d->mui); free(d->mui_old); free(d->hered); free(d->trees); free(d->b_locus); free(d->b_tree); free(d->b_br_off); free(d->b_nd_off);
   free(d->t_br_off); free(d->t_nd_off);
   free(d->b_logpr); free(d->p_logpr); free(d->p_delta); free(d->p_slot); free(d->u_pop);
   free(d->w_br); free(d->w_nd); free(d->w_nb); free(d->w_nn); free(d->w_hast); free(d->w_logpr); free(d->w_diff);
@@ -463,6 +467,7 @@ static int climb(const a00_driver_t * d, int p, double t)
 static double tree_logpr_stats(const a00_driver_t * d, const a00_tree_t * t, int * nc_out, double * t2h_out)
 {
   int nin[A00_MAXPOP], nc[A00_MAXPOP], p, k; double times[MAXN], logpr = 0;
+  const double h = d->hered ? d->hered[t - d->trees] : 1.0;         /* the locus's heredity scalar */
   for (p = 0; p < d->npop; ++p) nin[p] = 0;
   for (k = 0; k < t->tips; ++k) nin[t->pop[k]]++;
   for (p = 0; p < d->npop; ++p)
@@ -486,13 +491,23 @@ static double tree_logpr_stats(const a00_driver_t * d, const a00_tree_t * t, int
          stand still during a step's per-locus loop: every locus would take the same logarithm again) */
       {
         const double th = d->theta[p]; double term = 0;
-        if (n)
+        if (h == 1.0)
         {
-          a00_driver_t * dm = (a00_driver_t *)d;
-          if (dm->l2t_of[p] != th) { dm->l2t[p] = log(2.0/(1.0*th)); dm->l2t_of[p] = th; }      /* (threads race to store the same value) */
-          term += n*dm->l2t[p];
+          if (n)
+          {
+            a00_driver_t * dm = (a00_driver_t *)d;
+            if (dm->l2t_of[p] != th) { dm->l2t[p] = log(2.0/(1.0*th)); dm->l2t_of[p] = th; }      /* (threads race to store the same value) */
+            term += n*dm->l2t[p];
+          }
+          if (T2h) term -= T2h/(th*1.0);
         }
-        if (T2h) term -= T2h/(th*1.0);
+        else
+        {
+          /* gtree.c:3938-3943: heredity*theta first; the cache is keyed by theta alone, so this locus takes its logarithm in place */
+          const double thh = h*th;
+          if (n) term += n*log(2.0/thh);
+          if (T2h) term -= T2h/thh;
+        }
         logpr += term;
       }
     }
@@ -836,10 +851,11 @@ static int theta_step_all(a00_driver_t * d)
   for (li = 0; li < (long)d->nloci; ++li)
   {
     int nc[A00_MAXPOP], pp; double t2h[A00_MAXPOP];
+    const double h = d->hered ? d->hered[li] : 1.0;
     (void)tree_logpr_stats(d, d->trees + li, nc, t2h);
     for (pp = 0; pp < d->npop; ++pp)
       if (d->has_theta[pp])
-        d->w_diff[(size_t)li*A00_MAXPOP + pp] = a00_msc_term(nc[pp], t2h[pp], tnew[pp], 1.0) - a00_msc_term(nc[pp], t2h[pp], d->theta[pp], 1.0);
+        d->w_diff[(size_t)li*A00_MAXPOP + pp] = a00_msc_term(nc[pp], t2h[pp], tnew[pp], h) - a00_msc_term(nc[pp], t2h[pp], d->theta[pp], h);
   }
   for (i = 0; i < d->nloci; ++i)                          /* the sums in locus order, whatever the thread count */
     for (p = 0; p < d->npop; ++p)
@@ -857,8 +873,8 @@ static int theta_step_all(a00_driver_t * d)
   return 1;
 }
 
-/* k_p = coalescences in p, T_p = sum of T2h (2^-40 fixed point) over all loci, for the populations with a theta;
-   returns 0 when a term is unusable (the device's rule: |T2h| >= 256) */
+/* k_p = coalescences in p, T_p = sum of T2h/h_i (2^-40 fixed point; the division first, as C2h_sum in stree.c:3679) over all
+   loci, for the populations with a theta; returns 0 when a term is unusable (the device's rule: |T2h/h| >= 256) */
 static int theta_sums(a00_driver_t * d, long long * ksum, long long * tsum)
 {
   int p, bad = 0; long li;
@@ -875,8 +891,9 @@ static int theta_sums(a00_driver_t * d, long long * ksum, long long * tsum)
       for (pp = 0; pp < d->npop; ++pp)
         if (d->has_theta[pp])
         {
-          if (!(fabs(t2h[pp]) < 256.0)) badl = 1;
-          else { kl[pp] += nc[pp]; tl[pp] += llrint(t2h[pp]*1099511627776.0); }
+          const double x = d->hered ? t2h[pp]/d->hered[li] : t2h[pp];
+          if (!(fabs(x) < 256.0)) badl = 1;
+          else { kl[pp] += nc[pp]; tl[pp] += llrint(x*1099511627776.0); }
         }
     }
 #pragma omp critical
@@ -984,7 +1001,8 @@ static int tau_step(a00_driver_t * d, int q)
     {
       int nc[A00_MAXPOP]; double t2h[A00_MAXPOP]; int jj;
       d->p_logpr[i] = tree_logpr_stats(d, t, nc, t2h);
-      for (jj = 0; jj < 3; ++jj) d->w_diff[(size_t)i*A00_MAXPOP + jj] = d->p_logpr[i] == d->p_logpr[i] ? t2h[aff[jj]] : NAN;
+      for (jj = 0; jj < 3; ++jj)           /* (stree.c:5888, 5926: C2ji/heredity) */
+        d->w_diff[(size_t)i*A00_MAXPOP + jj] = d->p_logpr[i] == d->p_logpr[i] ? (d->hered ? t2h[aff[jj]]/d->hered[i] : t2h[aff[jj]]) : NAN;
       d->p_delta[i] = below*lminf + above*lmaxf;
     }
     else
@@ -1326,6 +1344,64 @@ static int mubar_step(a00_driver_t * d)
   return 1;
 }
 
+/* ---- heredity scalars (bpp_amd_host.h): h_i of 'heredity = 1 a b' (estimated) or 'heredity = 2 file' (fixed) */
+int a00_set_heredity(a00_driver_t * d, const double * h)
+{
+  unsigned i;
+  if (!h || d->initialized) return 0;                     /* (the start-up densities have used the scalars) */
+  for (i = 0; i < d->nloci; ++i) if (!(h[i] > 0) || !(h[i] < INFINITY)) return 0;
+  if (!d->hered && !(d->hered = (double *)calloc(d->nloci, sizeof(double)))) return 0;
+  for (i = 0; i < d->nloci; ++i) d->hered[i] = h[i];
+  return 1;
+}
+void a00_get_heredity(const a00_driver_t * d, double * h)
+{
+  unsigned i;
+  if (h) for (i = 0; i < d->nloci; ++i) h[i] = d->hered ? d->hered[i] : 1.0;
+}
+int a00_set_heredity_move(a00_driver_t * d, double ft_h, double a, double b)
+{
+  if (!(ft_h >= 0) || !(ft_h < INFINITY)) return 0;
+  if (ft_h > 0 && (!(a > 0) || !(b > 0) || !(a < INFINITY) || !(b < INFINITY))) return 0;
+  d->ft_h = ft_h; d->h_a = a; d->h_b = b;
+  return 1;
+}
+void a00_heredity_counters(const a00_driver_t * d, unsigned long * proposed, unsigned long * accepted)
+{
+  if (proposed) *proposed = d->h_prop;
+  if (accepted) *accepted = d->h_acc;
+}
+
+/* HRDT: the heredity scalar of every locus (prop_heredity, gtree.c:8214): sliding window reflected at 0, gamma(a, b) prior,
+   the locus's own MSC density at h' against the stored one; window and acceptance number from the locus's own stream; no
+   likelihood work.  An h' that is 0 or not finite is rejected (the uniform kernel still takes its acceptance number) */
+static int hered_step(a00_driver_t * d)
+{
+  long li;
+  if (!d->hered)
+  {
+    unsigned i;
+    if (!(d->hered = (double *)calloc(d->nloci, sizeof(double)))) return 0;
+    for (i = 0; i < d->nloci; ++i) d->hered[i] = 1.0;
+  }
+#pragma omp parallel for schedule(static) num_threads(d->threads) if (d->threads > 1)
+  for (li = 0; li < (long)d->nloci; ++li)
+  {
+    a00_tree_t * t = d->trees + li;
+    const double hold = d->hered[li];
+    const double hnew = fabs(hold + d->ft_h*draw_window(d, li));
+    double logpr, lnacc;
+    d->w_nb[li] = 0;
+    if (!(hnew > 0) || !(hnew < INFINITY)) { skip_u(d, li); continue; }
+    d->hered[li] = hnew;
+    logpr = tree_logpr(d, t);
+    lnacc = ((d->h_a - 1)*log(hnew/hold) - d->h_b*(hnew - hold)) + (logpr - t->logpr);
+    if (accept(d, li, lnacc, -1.0)) { t->logpr = logpr; d->w_nb[li] = 1; } else d->hered[li] = hold;
+  }
+  for (li = 0; li < (long)d->nloci; ++li) { d->h_prop++; d->h_acc += (unsigned long)d->w_nb[li]; }      /* (no shared writes in the loop) */
+  return 1;
+}
+
 int a00_iterate(a00_driver_t * d)
 {
   unsigned i; int k, maxtips = 0;
@@ -1344,6 +1420,8 @@ int a00_iterate(a00_driver_t * d)
   if (d->theta_alpha > 0 && !theta_step_all(d)) return 0;
   for (k = d->S; k < d->npop; ++k)    if (!tau_step(d, k)) return 0;
   if (!mix_step(d)) return 0;
+  /* the heredity scalars after MIX, before the substitution parameters (method.c:5616-5621) */
+  if (d->ft_h > 0 && !hered_step(d)) return 0;
   /* the substitution-parameter moves come last (method.c:5699-5735) */
   if (d->sm && d->setpar)
   {

@@ -1038,13 +1038,14 @@ __global__ void __launch_bounds__(1024) sum_decide_kernel(const double * __restr
 // THETA (theta_step_all of a00_driver.c): one workgroup per population.  The per-locus terms come from the sufficient
 // statistics the sweep left behind (no tree is loaded), are summed in a fixed order and the population's own decision
 // is taken right here — the thetas are conditionally independent given the gene trees.  ext_sum != NULL: the sums were
-// made (and all-reduced over the ranks) beforehand, only decide.
+// made (and all-reduced over the ranks) beforehand, only decide.  hered != NULL (the generic sampler with heredity scalars): a
+// locus whose h_i is not 1 takes its two terms at h_i theta (a00_msc_term with the locus's scalar, as theta_step_all does).
 struct ThetaArgs { double win_u[MAXPOP], uacc[MAXPOP]; uint32_t on[MAXPOP]; };
 
 __global__ void __launch_bounds__(1024) theta_sum_decide_kernel(const int8_t * __restrict__ pop_nc, const double * __restrict__ pop_t2h,
                                                                 uint32_t T, double * taus, Species sp, ThetaArgs ta,
                                                                 uint32_t * counters, double * sums_out, const double * ext_sum,
-                                                                int decide_on)
+                                                                int decide_on, const double * __restrict__ hered)
 {
   __shared__ double sh[1024];
   const int p = (int)blockIdx.x;
@@ -1060,7 +1061,9 @@ __global__ void __launch_bounds__(1024) theta_sum_decide_kernel(const int8_t * _
     for (uint32_t i = threadIdx.x; i < T; i += 1024)
     {
       const int nc = pop_nc[(size_t)p*T + i]; const double t2h = pop_t2h[(size_t)p*T + i];
-      acc += msc_term(nc, t2h, tnew, l2t_new) - msc_term(nc, t2h, told, l2t_old);
+      const double h = hered ? hered[i] : 1.0;
+      if (h == 1.0) acc += msc_term(nc, t2h, tnew, l2t_new) - msc_term(nc, t2h, told, l2t_old);
+      else { const double hn = h*tnew, ho = h*told; acc += msc_term(nc, t2h, hn, log(2.0/hn)) - msc_term(nc, t2h, ho, log(2.0/ho)); }
     }
     sh[threadIdx.x] = acc;
     __syncthreads();
@@ -1195,6 +1198,13 @@ struct bpa_sampler
   DevBuf<double> g_mui, g_mui_old;
   DevBuf<gsm::GLrState> g_lr;
   double g_lr_ft[2] = {0, 0}, g_a_mui = 0, g_a_mubar = 0, g_b_mubar = 0;
+  // heredity scalars (bpa_sampler_set_heredity / bpa_sampler_set_heredity_move): [T] doubles in an array of their own, never made
+  // when no scalar is set and the move is off; the host copy is level with the device after a download.  Every locus is proposed
+  // once per HRDT step: the proposals are counted here, the acceptances in the trees (pj_hered_acc)
+  std::vector<double> g_hered_host;
+  DevBuf<double> g_hered;
+  double g_h_ft = 0, g_h_a = 0, g_h_b = 0;
+  unsigned long g_h_prop = 0;
   bool g_eigen_dirty = false;
   bool g_level_eval = false;            // gs_level_roots: this evaluation stores every parent
   bool g_root_stale = false;            // a step's evaluation left the root's CLV unstored (flags bit 11): gs_download brings the buffers level
@@ -1391,7 +1401,7 @@ extern "C" void bpa_sampler_destroy(bpa_sampler_t * s)
   s->g_dev.free(); s->g_undo.free(); s->g_loc.free(); s->g_lnl.free(); s->g_lnlcur.free(); s->g_hast.free(); s->g_logpr.free(); s->g_delta.free(); s->g_site.free();
   s->g_len.free(); s->g_lograt.free(); s->g_active.free(); s->g_recs.free(); s->g_mat2.free(); s->g_bmo.free();
   s->g_sm.free(); s->g_sm_old.free(); s->g_ids.free();
-  s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free();
+  s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free(); s->g_hered.free();
   s->b_dev.free(); s->b_undo.free(); s->b_thr.free();
   s->g_ops20.free(); s->g_oprng.free(); s->g_root20.free(); s->g_mtask.free(); s->g_mpm.free(); s->g_tlocus.free(); s->g_tpat.free(); s->g_ttask.free(); s->g_tn0.free(); s->g_rscaler.free();
   s->v2_wave_off.free(); s->v2_loc.free(); s->v2_pat.free(); s->v2_xbuf.free(); s->v2_grng.free(); s->v2_err.free(); s->v2_prof.free(); s->v2_sched.free(); s->v2_declog.free(); s->v2_sp.free();
@@ -2390,6 +2400,9 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
   // the locus-rate moves decide from the sum of ONE rank's rates: refused with several ranks, before anything is launched
   if (s->generic && (s->g_lr_ft[0] > 0 || s->g_lr_ft[1] > 0) && (s->allreduce || s->p2p))
     return fail("bpa_sampler_iterate: the locus-rate moves run on one rank (an all-reduce callback or the mailboxes are installed: the sum of the rates over the ranks is not exchanged)");
+  // the heredity move decides per locus, but its scalars enter the THETA / TAU sums the ranks exchange: one rank only, as the rates
+  if (s->generic && s->g_h_ft > 0 && (s->allreduce || s->p2p))
+    return fail("bpa_sampler_iterate: the heredity move runs on one rank (an all-reduce callback or the mailboxes are installed)");
   if (!sampler_upload(s)) return 0;
   s->host_current = false;
   if (s->big) return gb_iterate(s, iterations);
@@ -2417,11 +2430,11 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
         if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
       if (!s->allreduce)
         hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1);
+                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)nullptr);
       else
       {
         hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0);
+                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0, (const double *)nullptr);
         // all populations' sums in ONE collective, in the memory the callback's collective addresses
         double * ar = s->sum_ext ? s->sum_ext : s->theta_sums.p;
         const size_t nb = (size_t)s->sp.npop*sizeof(double);
@@ -2429,7 +2442,7 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
         if (!s->allreduce(s->allreduce_ctx, ar, (unsigned)s->sp.npop, (void *)e->stream)) return fail("bpa_sampler: the all-reduce callback failed");
         if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(s->theta_sums.p, ar, nb, hipMemcpyDeviceToDevice, e->stream));
         hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1);
+                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1, (const double *)nullptr);
       }
       s->logpr_stale = true;        // the next launch (any mode) recomputes every tree's density with the new thetas
       HIPCHK(hipGetLastError());

@@ -468,6 +468,30 @@ int  bpa_sampler_set_locus_rates(bpa_sampler_t *, const double * mui /* [nloci] 
 int  bpa_sampler_get_locus_rates(bpa_sampler_t *, double * mui /* [nloci] or NULL */, double * mubar /* or NULL */);
 int  bpa_sampler_set_locusrate_moves(bpa_sampler_t *, double ft_mui, double ft_mubar, double a_mui, double a_mubar, double b_mubar, double mubar);
 int  bpa_sampler_locusrate_counters(bpa_sampler_t *, unsigned long prop[2], unsigned long acc[2]);
+/* Heredity scalars: BPP's 'heredity = 2 file' (fixed, typically 1 / 0.75 / 0.25 for autosomal, X-linked and mitochondrial
+   loci) and 'heredity = 1 a b' (h_i ~ gamma(a, b), estimated).  The population size of locus i is h_i theta_p: population p's
+   term of the locus's MSC density is ncoal log(2/(h_i theta_p)) - T2h/(theta_p h_i), h_i theta_p formed first (gtree.c:3938-3943)
+   — in every proposal, in start-up and in the THETA decisions; the sums over loci the program's THETA / TAU / MIX decide from are
+   sums of T2h_i/h_i, divided before the 2^-40 fixed point (stree.c:3679, 5888, 5926; prop_mixing.c:359).  The likelihood does
+   not see the scalars.  A locus whose scalar is exactly 1.0 takes the code (and the table's log(2/theta)) it always did.
+     HRDT   prop_heredity, gtree.c:8214, after MIX and before the substitution-parameter moves (method.c:5616-5621): per locus
+            h' = |h + ft_h w|, window and acceptance number from the locus's own stream, lnacc = (a - 1) log(h'/h) - b (h' - h)
+            + logpr(h') - logpr(h); an h' that is 0 or not finite is rejected.  No likelihood work: one launch per part-batch
+            (step mode 10 of the generic sampler's lane-group kernel) proposes, decides and replaces the stored density.
+   Meanings as the host driver's a00_set_heredity / a00_get_heredity / a00_set_heredity_move / a00_heredity_counters
+   (bpp_amd_host.h): scalars [nloci], each > 0 and finite, before bpa_sampler_initialize (ft_h = 0 keeps them fixed); ft_h is the
+   window width (the program borrows finetune_locusrate), 0 = off (the default), a, b > 0 while it is on, changeable at any
+   time; the counters are apart from bpa_sampler_summary's totals (bpa_sampler_burnin does not adapt ft_h: apply
+   bpa_finetune_onestep to them).  Heredity scalars and locus rates may be on together.  A sampler on which none of this is
+   called computes what it always did, to the bit.
+   The generic sampler only (BPA_SAMPLER_GENERIC; BPA_SMP_GENERIC=1 makes it take loci the LDS kernels would otherwise): scalars
+   or a non-zero width on any other kind fail (a width of 0 is "nothing asked for": 1), as do a scalar <= 0 or not finite, a or
+   b <= 0 while the move is on, scalars after bpa_sampler_initialize, and — when bpa_sampler_iterate is called, before any
+   launch — the move together with an all-reduce callback (one rank only).  Each returns 1, or 0 with bpa_last_error set.     */
+int  bpa_sampler_set_heredity(bpa_sampler_t *, const double * h /* [nloci] */);
+int  bpa_sampler_get_heredity(bpa_sampler_t *, double * h /* [nloci] */);
+int  bpa_sampler_set_heredity_move(bpa_sampler_t *, double ft_h, double a, double b);
+int  bpa_sampler_heredity_counters(bpa_sampler_t *, unsigned long * proposed, unsigned long * accepted);
 /* measurement: HIP start/stop events on every stride-th launch of the sampler's likelihood-carrying kernels
    (stride 0 = off); bpa_sampler_timing returns the milliseconds and launch counts accumulated since, by kind: the
    sweep (the per-locus GAGE + GSPR proposals of an iteration, one launch) and the all-loci steps (TAU, MIX)       */

@@ -446,6 +446,27 @@ void           a00_get_locus_rates(const a00_driver_t *, double * mui /* [nloci]
 int            a00_set_locusrate_moves(a00_driver_t *, double ft_mui, double ft_mubar, double a_mui, double a_mubar, double b_mubar, double mubar);
 void           a00_locusrate_counters(const a00_driver_t *, unsigned long prop[2], unsigned long acc[2]);
 
+/* ---- heredity scalars: BPP's 'heredity = 1 a b' (h_i ~ gamma(a, b), estimated) and 'heredity = 2 file' (fixed, typically 1 /
+   0.75 / 0.25 for autosomal / X-linked / mitochondrial loci).  The population size of locus i is h_i theta_p: population p's
+   term of the locus's MSC density is ncoal log(2/(h_i theta_p)) - T2h/(theta_p h_i), with h_i theta_p formed first
+   (gtree_update_logprob_contrib, gtree.c:3938-3943); the likelihood does not see the scalars.  Every sum over loci that the
+   program's THETA / TAU / MIX decide from is a sum of T2h_i/h_i, divided before the 2^-40 fixed-point conversion (C2h_sum,
+   stree.c:3679, 5888, 5926; prop_mixing.c:359); the coalescence counts stay.  A locus whose scalar is exactly 1.0 takes the
+   code (and the cached log(2/theta)) it always did.
+     HRDT    every locus, after MIX and before the substitution-parameter moves (method.c:5616-5621): h' = |h + ft_h w|, window and
+             acceptance number from the locus's own stream (the program's kernel draws the number only when needed, the uniform
+             one always); lnacc = (a - 1) log(h'/h) - b (h' - h) + logpr(h') - logpr(h); an h' that is 0 or not finite is
+             rejected; the locus's stored density is replaced on acceptance; no likelihood work (prop_heredity, gtree.c:8214)
+   a00_set_heredity: the starting (or, with ft_h = 0, fixed) scalars of all loci, each > 0 and finite, before a00_initialize; 0 on
+   a bad value or a driver already initialized.  Never called and the move off: every scalar is 1 and nothing of a trajectory
+   changes.  a00_set_heredity_move: the window width (0 = off, the default; the program borrows finetune_locusrate) and the
+   prior (a, b > 0 while the move is on) — at any time; 0 on a bad argument.  HRDT's proposals and acceptances are counted
+   apart from a00_counters' totals: a00_heredity_counters.  Heredity scalars and locus rates may be on together.              */
+int            a00_set_heredity(a00_driver_t *, const double * h /* [nloci] */);
+void           a00_get_heredity(const a00_driver_t *, double * h /* [nloci] */);
+int            a00_set_heredity_move(a00_driver_t *, double ft_h, double a, double b);
+void           a00_heredity_counters(const a00_driver_t *, unsigned long * proposed, unsigned long * accepted);
+
 /* start-up evaluation: all matrices, all partials, lnL (method.c:4285-4297) */
 int            a00_initialize(a00_driver_t *);
 /* one iteration: GAGE over inner nodes, GSPR over non-root nodes, THETA per population (if a prior is set),
