@@ -39,8 +39,20 @@ those that pass by the 5e-16 absolute bar instead; logpr was 0.0 in every case, 
     ... 12 and 16 tips side by side    200     6  .55-.60  0.0       0.0          0.0       3       0.0
   big, 17 tips, 30 / 300 patterns       30     3  .30-.50  0.0       0.0          0.0       0       0.0
   big, 64 tips, 30 / 300 patterns       30     3  .25-.47  0.0       0.0          0.0       0       1.1e-16
-  (generic: BPA_GS_CHAIN=0 and 1 gave the same figures; big: with and without scale buffers gave the same figures, and no scale
-  counter of the oracle's recompute was non-zero at 17 or 64 tips on these loci)
+  where the scale counters fire (tests/test_gpu_scaling_fires.py on the sets of tests/firing.py, big-tree sampler with scale buffers,
+  uniform / program's moves; `nodes`: inner nodes with a non-zero counter in the ORACLE's recompute, per locus, after the first
+  iteration -> after the last; `top`: the largest counter at the start tree -> after the last):
+  case                          iterations  loci   acc   lnl       root buffer  total     P ulps  P abs    nodes                top
+  big, 17 + 24 tips, f = 1e-6           30   3+3  .31-.38  0.0     0.0          0.0       0       0.0      2-6 -> 1-7           2 -> 1
+  big, 24 tips, f = 1e-6                30     6  .29-.37  0.0     0.0          0.0       0       0.0      2-6 -> 1-7           2 -> 1
+  big, 24 tips, GTR+G4, f = 1e-6        30     6  .30-.37  0.0     0.0          0.0       0       0.0      2-5 -> 1-4           2 -> 1
+  big, 64 tips, f = 1e-3                30     3  .28-.34  0.0     0.0          0.0       0       0.0      4-6 -> 3-6           3 -> 2-3
+  (at branch lengths of 1e-10 .. 1e-8 expm1(x) is x on both sides: every P-matrix, and with it every lnL, had the oracle's bits; the
+  batched plans, the tapes — 220 steps per locus, JC69 and GTR+G4 — and the host driver's 5 iterations of that file were 0.0 from the
+  oracle / the reference as well)
+  (generic: BPA_GS_CHAIN=0 and 1 gave the same figures; big: with and without scale buffers gave the same figures.  On the loci of
+  tests/shapes.py no scale counter of the oracle's recompute is non-zero at 17 or 64 tips — those cases compare zeros; the counters
+  that are non-zero are the four cases above and the golden loci 9-11 / K1 vectors of tests/test_gpu_parity.py)
 
 No invariant failed on the device.  Reads between iterations (the last test): on the library before the marks of
 gs_mark_roots, all 180 reads (60 loci x single-locus call / plan / batch) of the buffer the tree then named as the root's returned
