@@ -150,11 +150,10 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
   if (prog && !gs_prog_ready(s)) return 0;
   for (unsigned it = 0; it < iterations; ++it)
   {
-    const unsigned ngage = s->env_gage >= 0 ? (unsigned)s->env_gage : s->maxtips - 1, ngspr = s->env_gspr >= 0 ? (unsigned)s->env_gspr : 2*s->maxtips - 2;   // (BPA_SMP_STEPS: diagnostics)
+    const unsigned ngage = s->maxtips - 1, ngspr = 2*s->maxtips - 2;
     for (unsigned k = 0; k < ngage; ++k)   { if (!gb_step(s, 0, k) || !gb_eval(s, 0)) return 0; }
     for (unsigned k = 0; k < ngspr; ++k)   { if (!gb_step(s, 1, k) || !gb_eval(s, 0)) return 0; }
     s->sweeps++;
-    if (s->env_nomix) continue;
     if (prog)
     {
       // THETA / TAU / MIX as the program runs them (gs_iterate's device-decided branch): the host is paced two iterations behind

@@ -221,9 +221,8 @@ static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, u
   c->cb.resize(n); c->ctx.resize(n); c->state.assign(n, 2); c->result.assign(n, 0); c->pend_ptr.assign(n, nullptr); c->pend_n.assign(n, 0);
   c->stacks.resize(n);
   c->stream.assign(n, e->stream); c->ev_part.assign(n, nullptr);
-  const bool one_stream = BPA_EXP_SWITCH("BPA_COMP_ONE_STREAM") != nullptr;
   if (hipEventCreateWithFlags(&c->ev_sum, hipEventDisableTiming) != hipSuccess) c->ev_sum = nullptr;
-  for (size_t i = 1; i < n && !one_stream; ++i)
+  for (size_t i = 1; i < n; ++i)
   {
     hipStream_t st = nullptr;
     if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); continue; }        // (the part then runs on the engine's stream)

@@ -231,15 +231,6 @@ static int set_device(bpa_engine * e)
 // ------------------------------------------------------------------ engine --
 extern "C" const char * bpa_version(void) { return "bpp_amd 0.1 (gfx950)"; }
 extern "C" const char * bpa_last_error(void) { return g_err.c_str(); }
-// 1: built with -DBPA_EXPERIMENTAL (csrc/experimental/ compiled, the A/B switches of superseded variants read from the environment)
-extern "C" int bpa_experimental_build(void)
-{
-#ifdef BPA_EXPERIMENTAL
-  return 1;
-#else
-  return 0;
-#endif
-}
 extern "C" void bpa_internal_set_error(const char * msg) { g_err = msg ? msg : ""; }   // host_input.cpp
 
 extern "C" int bpa_device_count(void)
@@ -351,9 +342,8 @@ extern "C" bpa_locus_t * bpa_locus_create(bpa_engine_t * e, unsigned dtype, unsi
   const size_t w_bytes = up16(Np*sizeof(uint32_t)), tip_bytes = up16((size_t)tips*Np*l->code_bytes());
   const size_t pm_bytes = (size_t)prob_matrices*R*d.pstride*sizeof(double);
   char * hot = (char *)e->arena.alloc(par_bytes + w_bytes + tip_bytes + (jc69 ? pm_bytes : 0), 128);
-  // 20-state CLVs are state-major planes: pad the plane stride to whole 128-byte lines (BPA_NO_PLANE_PAD=1: the first layout)
-  static const bool no_pad = BPA_EXP_SWITCH("BPA_NO_PLANE_PAD") && atoi(BPA_EXP_SWITCH("BPA_NO_PLANE_PAD"));
-  const size_t Ld = (S == 20 && !no_pad) ? up16(Np) : Np;
+  // 20-state CLVs are state-major planes: pad the plane stride to whole 128-byte lines
+  const size_t Ld = S == 20 ? up16(Np) : Np;
   d.ld = (uint32_t)Ld;
   d.clv    = (double *)e->arena.alloc(std::max<size_t>(clv_buffers, 1)*R*Ld*S*sizeof(double), 128);
   d.scaler = scale_buffers ? (uint32_t *)e->arena.alloc((size_t)scale_buffers*Np*sizeof(uint32_t), 128) : nullptr;
@@ -750,9 +740,6 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
   p->eng = e;
   p->bytes_partials = p->bytes_pmatrix = p->flops_partials = p->bytes_codes = 0; p->node_updates = p->pattern_updates = 0;     // (a plan object may be rebuilt)
   p->fused_klane = p->fused_jc69 = p->jc69_v2 = p->klane_v2 = false; p->fused_rt = 0;
-  static const bool prof = BPA_EXP_SWITCH("BPA_PLAN_PROF") != nullptr;
-  auto tprev = std::chrono::steady_clock::now();
-  auto lap = [&](const char * what) { if (!prof) return; const auto tn = std::chrono::steady_clock::now(); fprintf(stderr, "[plan] %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(tn - tprev).count()); tprev = tn; };
   std::vector<uint32_t> locus(T), pat_off(T + 1, 0), mat_task;
   p->states = b->loci[0]->states;
   p->rmax = 1;
@@ -813,7 +800,6 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
       p->bytes_codes += (fwd ? 0.0 : Np*R*S*8) + 4*Np;
     }
   }
-  lap("validate");
   const unsigned P = pat_off[T];
   p->h_locus = locus;
   std::vector<int32_t> rs(T, BPA_SCALE_BUFFER_NONE);
@@ -836,7 +822,6 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
   if (!p->thr_task.reserve(P) || !p->site_term.reserve(P) || !p->lnl.reserve(T))
     return fail("out of device memory (plan)");
 
-  lap("csr uploads");
   PlanDev & d = p->pd;
   d.task_locus = p->task_locus.p; d.task_pat_off = p->task_pat_off.p; d.thr_task = p->thr_task.p;
   d.mat_off = p->mat_off.p; d.mat_task = p->mat_task.p; d.mat_pmatrix = p->mat_pmatrix.p;
@@ -849,24 +834,20 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
 
   // tiled path (20 states): one workgroup per 128-pattern tile of one locus
   p->ntiles = 0; d.tile_task = d.tile_n0 = nullptr;
-  // 20-state partials kernel (kernels.hpp): the pipelined kernel (partials_lnl_pipe20_kernel: P-matrices global -> LDS
-  // direct and double-buffered, one wave per rate category, CLV planes streamed, 2 waves per SIMD).  BPA_S20_KERNEL
-  // selects the others, kept for comparison and as fall-backs: pipemfma (the same update on the matrix cores, on the same
-  // memory pipeline) | tiled (one wave runs all categories: what loci of more than 4 categories get) | generic (no staging)
+  // 20-state partials kernel (kernels.hpp): the wave kernel (partials_lnl_wave20_kernel: one wave per rate category, CLV
+  // planes streamed).  BPA_S20_KERNEL selects the others, kept for comparison and as fall-backs: pipemfma (the same update
+  // on the matrix cores) | tiled (one wave runs all categories: what loci of more than 4 categories get)
   {
     const char * v = getenv("BPA_S20_KERNEL");
     p->s20_kernel = v ? v : "wave";
-    if (p->s20_kernel != "wave" && p->s20_kernel != "waverl" && p->s20_kernel != "wave2" && p->s20_kernel != "pipe" && p->s20_kernel != "pipemfma" && p->s20_kernel != "tiled" && p->s20_kernel != "generic") p->s20_kernel = "wave";
-#ifndef BPA_EXPERIMENTAL
-    // (the default build holds the default, north_star's matrix-core kernel and the fall-back of loci with more than 4 categories;
-    //  waverl / wave2 / pipe / generic are csrc/experimental's: asking for one of them here is an error, not a silent default)
-    if (p->s20_kernel != "wave" && p->s20_kernel != "pipemfma" && p->s20_kernel != "tiled")
-      return fail("BPA_S20_KERNEL: this 20-state kernel is part of an experimental build only (-DBPA_EXPERIMENTAL)");
-#endif
+    // (waverl / wave2 / pipe / generic were removed: asking for one of them is an error, not a silent default)
+    if (p->s20_kernel == "waverl" || p->s20_kernel == "wave2" || p->s20_kernel == "pipe" || p->s20_kernel == "generic")
+      return fail("BPA_S20_KERNEL: this 20-state kernel variant was removed (wave, pipemfma and tiled remain)");
+    if (p->s20_kernel != "pipemfma" && p->s20_kernel != "tiled") p->s20_kernel = "wave";
   }
-  p->s20_tiledk = p->s20_kernel == "wave" || p->s20_kernel == "waverl" || p->s20_kernel == "wave2" || p->s20_kernel == "pipe" || p->s20_kernel == "pipemfma";
+  p->s20_tiledk = p->s20_kernel != "tiled";
   if (p->s20_tiledk && p->rmax > 4) { p->s20_tiledk = false; p->s20_kernel = "tiled"; }     // 64 x R lanes must fit a 256-lane workgroup
-  p->tile = (p->s20_tiledk && p->s20_kernel != "wave2") ? 64 : 128;       // (wave2: two patterns per lane)
+  p->tile = p->s20_tiledk ? 64 : 128;
   if (p->states == 20)
   {
     std::vector<uint32_t> tt, tn;
@@ -886,10 +867,9 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
   {
     // workgroup size (lanes = patterns, whole loci per workgroup)
     unsigned BS = maxnp <= 16 ? 256 : (maxnp <= 64 ? 64 : 256);     // measured: config 2 +3 % with 256, config 3 +8 % with 64
-    if (const char * ov = BPA_EXP_SWITCH("BPA_FUSED_BS")) { const unsigned v = (unsigned)atoi(ov); if ((v == 64 || v == 256) && maxnp <= v) BS = v; }
     // one lane per (pattern, rate category) when every locus has several categories, no scalers and no
     // phase averaging (step_s4_klane_kernel)
-    bool klane = p->rmax > 1 && !BPA_EXP_SWITCH("BPA_NO_KLANE");
+    bool klane = p->rmax > 1;
     unsigned maxlanes = 0;
     for (unsigned t = 0; t < T && klane; ++t)
     {
@@ -972,7 +952,6 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
           m.par = l->dev.par; m.rate_cats = l->rate_cats; m.model = l->dev.model; m.entry = i; m.pad = 0;
         }
     }
-    lap("records (host)");
     if (!upload(p->recs, recs.data(), recs.size())) return 0;
     if (!upload(p->lane_rec, lane_rec.data(), lane_rec.size())) return 0;
     task_rec[T] = (uint32_t)recs.size();
@@ -980,13 +959,12 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
     if (!upload(p->mat_recs, mrecs.data(), nmat)) return 0;
     d.recs = p->recs.p; d.lane_rec = p->lane_rec.p; d.task_rec = p->task_rec.p; d.mat_recs = p->mat_recs.p;
     p->fused_rt = all1 ? 1 : (all4 ? 4 : 0);
-    lap("records (upload)");
-    p->fused_jc69 = all1 && all_jc && !BPA_EXP_SWITCH("BPA_NO_JC69_FAST");
+    p->fused_jc69 = all1 && all_jc;
     d.pad = p->rmax;
 
     // compact records over the engine's packing (step_jc69_v2_kernel): the plan's loci must be packed and come in slot order
     p->jc69_v2 = p->klane_v2 = false;
-    if ((p->fused_jc69 && !BPA_EXP_SWITCH("BPA_JC69_V1")) || (p->fused_klane && !BPA_EXP_SWITCH("BPA_KLANE_V1")))
+    if (p->fused_jc69 || p->fused_klane)
     {
       if (!engine_pack(e)) return 0;
       bool ok = e->pack_slots > 0;
@@ -1049,7 +1027,6 @@ static int plan_build(bpa_plan * p, bpa_engine * e, const bpa_batch_t * b)
     }
   }
 
-  lap("v2 / rest");
   hipLaunchKernelGGL(build_thr_task_kernel, dim3((P + BPA_BLOCK - 1)/BPA_BLOCK), dim3(BPA_BLOCK), 0, e->stream,
                      p->task_pat_off.p, T, P, p->thr_task.p);
   HIPCHK(hipGetLastError());
@@ -1091,12 +1068,11 @@ static int timing_drain(bpa_engine * e)
 // mode bits: 1 = P-matrices, 2 = partials (+ per-pattern lnL terms), 4 = per-locus reduction
 // the K1 + K2 launch of the compact-record path for loci of several rate categories: step_s4_klane_v3_kernel (the step's
 // records and all its P-matrices in LDS, three global round trips per step) wherever a slot record fits the 16 units a
-// lane group brings in one load — loci of up to 16 tips —, step_s4_klane_v2_kernel otherwise (BPA_KLANE_V2=1: always, A/B)
+// lane group brings in one load — loci of up to 16 tips —, step_s4_klane_v2_kernel otherwise
 template <bool FUSE_A>
 static void launch_klane(const dim3 grid, hipStream_t st, hipEvent_t k0, hipEvent_t k1, const PlanDev & d)
 {
-  static const bool env_v2 = BPA_EXP_SWITCH("BPA_KLANE_V2") != nullptr;
-  if (!env_v2 && d.rec2_units >= 2u && d.rec2_units <= 16u)
+  if (d.rec2_units >= 2u && d.rec2_units <= 16u)
   {
     const size_t lds = (size_t)(PACK_BS/64)*BPA_KLANE_CH*1024u;            // (the wave's corner holds the matrices of BPA_KLANE_CH updates at a time)
     hipExtLaunchKernelGGL((step_s4_klane_v3_kernel<PACK_BS, FUSE_A>), grid, dim3(PACK_BS), lds, st, k0, k1, 0, d);
@@ -1107,8 +1083,6 @@ static void launch_klane(const dim3 grid, hipStream_t st, hipEvent_t k0, hipEven
 
 static int plan_launch_mode(bpa_plan * p, int mode)
 {
-  // A/B switches of DESIGN.md's appendix, read once
-  static const bool env_fused_split = BPA_EXP_SWITCH("BPA_FUSED_SPLIT") != nullptr;
   bpa_engine * e = p->eng;
   if (e->stale_roots)                       // (a plan made before the sampler ran)
     for (uint32_t id : p->h_locus) if (!roots_level(e, &e->loci[id], 1, "plan")) return 0;
@@ -1139,17 +1113,13 @@ static int plan_launch_mode(bpa_plan * p, int mode)
       if (d.flags & 1u)
       {
         PlanDev da = d; da.flags = 1u;
-        static const bool pm_packed = BPA_EXP_SWITCH("BPA_PMAT_PACKED") != nullptr;        // A/B: the phase on the packing's workgroups
-        if (pm_packed) hipLaunchKernelGGL((step_s4_klane_v2_kernel<PACK_BS, true>), g2, dim3(PACK_BS), 0, e->stream, da);
-        else hipLaunchKernelGGL(pmatrix_s4_dense_kernel, dim3((d.nmat*std::max(da.pad, 1u) + 255u)/256u), dim3(256), 0, e->stream, da, d.nmat);
+        hipLaunchKernelGGL(pmatrix_s4_dense_kernel, dim3((d.nmat*std::max(da.pad, 1u) + 255u)/256u), dim3(256), 0, e->stream, da, d.nmat);
       }
       d.flags &= 6u;
       if (d.flags)
       {
-        static const bool klane_direct = BPA_EXP_SWITCH("BPA_KLANE_DIRECT") != nullptr;     // A/B: no LDS staging of the P-matrices
-        if (klane_direct) d.flags |= 16u;
         if ((mode & 4) && p->sum_out && p->sum_parts == e->pack_blocks) { d.flags |= 8u; d.wg_part = p->sum_out; summed = true; }
-        // (register budget, measured with BPA_KLANE_OCC builds: the compiler's 126 VGPRs = 4 waves per SIMD 105 us; held to
+        // (register budget, measured with builds of other BPA_KLANE_OCC: the compiler's 126 VGPRs = 4 waves per SIMD 105 us; held to
         //  5 waves 121 us and to 6 waves 187 us (spills), to 3 waves 119 us)
         launch_klane<false>(g2, e->stream, k0, k1, d);
       }
@@ -1178,16 +1148,8 @@ static int plan_launch_mode(bpa_plan * p, int mode)
     }
     else if (p->fused_jc69)
     {
-      if (p->fused_bs == 64) hipExtLaunchKernelGGL((step_jc69_kernel<64, true>), grid, dim3(64), 0, e->stream, k0, k1, 0, d);
-      else                        hipExtLaunchKernelGGL((step_jc69_kernel<256, true>), grid, dim3(256), 0, e->stream, k0, k1, 0, d);
-    }
-    else if (p->fused_bs == 64 && p->fused_rt == 4 && (d.flags & 1u) && (d.flags & 6u) && env_fused_split)
-    {
-      // phase A on its own (no events), then B+C with the lighter register footprint
-      PlanDev da = d; da.flags = 1u;
-      hipLaunchKernelGGL((step_s4_fused_kernel<64, 4, 1>), grid, dim3(64), 0, e->stream, da);
-      d.flags &= 6u;
-      hipExtLaunchKernelGGL((step_s4_fused_kernel<64, 4, 6>), grid, dim3(64), 0, e->stream, k0, k1, 0, d);
+      if (p->fused_bs == 64) hipExtLaunchKernelGGL((step_jc69_kernel<64>), grid, dim3(64), 0, e->stream, k0, k1, 0, d);
+      else                        hipExtLaunchKernelGGL((step_jc69_kernel<256>), grid, dim3(256), 0, e->stream, k0, k1, 0, d);
     }
     else if (p->fused_bs == 64)
     {
@@ -1240,19 +1202,9 @@ static int plan_launch_mode(bpa_plan * p, int mode)
     else if (p->ntiles && p->s20_tiledk)
     {
       d.flags = 4u; d.pad = p->rmax;
-      static const bool no_xcd = BPA_EXP_SWITCH("BPA_NO_XCD_MAP") != nullptr;       // A/B: workgroup b = tile b
-      if (no_xcd) d.flags |= 32u;
       const dim3 grid(p->ntiles), block(64*p->rmax);
       if (p->s20_kernel == "pipemfma")
         hipLaunchKernelGGL((partials_lnl_pipemfma20_kernel<false, 2>), grid, block, ((size_t)4*p->rmax*400 + (size_t)p->rmax*64)*sizeof(double), e->stream, d);
-#ifdef BPA_EXPERIMENTAL
-      else if (p->s20_kernel == "pipe")
-        hipLaunchKernelGGL((partials_lnl_pipe20_kernel<20, true, 2>), grid, block, ((size_t)4*p->rmax*400 + (size_t)p->rmax*64)*sizeof(double), e->stream, d);
-      else if (p->s20_kernel == "waverl")
-        hipLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 2, 1, true>), grid, block, ((size_t)4*p->rmax*400 + (size_t)p->rmax*64)*sizeof(double), e->stream, d);
-      else if (p->s20_kernel == "wave2")
-        hipLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 1, 2>), grid, block, ((size_t)4*p->rmax*400 + (size_t)2*p->rmax*64)*sizeof(double), e->stream, d);
-#endif
       else
         hipLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 2>), grid, block, ((size_t)4*p->rmax*400 + (size_t)p->rmax*64)*sizeof(double), e->stream, d);
     }
@@ -1263,11 +1215,7 @@ static int plan_launch_mode(bpa_plan * p, int mode)
       hipLaunchKernelGGL((partials_lnl_tiled_kernel<20, 128>), dim3(p->ntiles), dim3(128), lds, e->stream, d);
     }
     else
-#ifdef BPA_EXPERIMENTAL
-      hipLaunchKernelGGL(partials_lnl_sN_kernel<20>, dim3(blocks), dim3(BPA_BLOCK), 0, e->stream, d);
-#else
-      return fail("no 20-state kernel for this plan (BPA_S20_KERNEL=generic is an experimental build's)");
-#endif
+      return fail("no 20-state kernel for this plan");
     HIPCHK(hipGetLastError());
   }
   if (ts) HIPCHK(hipEventRecord(ts->ev[2], e->stream));
@@ -1411,7 +1359,6 @@ extern "C" int bpa_plans_launch(bpa_plan_t * const * plans, unsigned count)
   if (!count) return 1;
   bpa_engine * e = plans[0]->eng;
   std::lock_guard<std::recursive_mutex> lock_(e->mtx);
-  static const bool no_chain = BPA_EXP_SWITCH("BPA_NO_CHAIN") != nullptr;
   if (!e->usedata) return 1;
   if (e->stale_roots)                       // (the chained launch below does not pass through plan_launch_mode)
     for (unsigned k = 0; k < count; ++k)
@@ -1421,7 +1368,7 @@ extern "C" int bpa_plans_launch(bpa_plan_t * const * plans, unsigned count)
   {
     // the longest run of consecutive chainable plans of this engine
     unsigned j = i;
-    if (!no_chain && plans[i]->eng == e && flush(e) && engine_pack(e))
+    if (plans[i]->eng == e && flush(e) && engine_pack(e))
       while (j < count && j - i < (unsigned)BPA_CHAIN_MAX && plans[j]->eng == e && chainable(plans[j])) ++j;
     if (j - i >= 2)
     {
@@ -1588,13 +1535,11 @@ extern "C" int bpa_plan_work(bpa_plan_t * p, double * bytes_partials, double * f
 // bpa_batch_evaluate's packed path in three parts (bpa_batch_begin / _fill / _end of the header): checks + sizing, the
 // record image of a range of the batch's loci (disjoint ranges from several threads at once: a locus's records go to its own
 // slot and its own range of the matrix list, nothing else is written), upload + launch + results.
-static double batch_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static int batch_begin_packed(bpa_engine * e, const bpa_batch_t * b, bool & handled, bool fast_ok = true)
 {
   handled = false;
   if (b->loci && !roots_level(e, b->loci, b->nloci, "batch")) return 0;
-  static const bool off = BPA_EXP_SWITCH("BPA_JC69_V1") != nullptr || BPA_EXP_SWITCH("BPA_NO_JC69_FAST") != nullptr;
-  if (off || !b->root_clv || !b->nloci) return 1;
+  if (!b->root_clv || !b->nloci) return 1;
   if (!flush(e) || !engine_pack(e)) return 0;
   if (!e->pack_slots || e->timing) return 1;
   const unsigned T = b->nloci;
@@ -1624,8 +1569,7 @@ static int batch_begin_packed(bpa_engine * e, const bpa_batch_t * b, bool & hand
     all_kl = all_kl && l->rate_cats > 1 && l->scale_buffers == 0 && !l->dev.unphased_length && (!b->root_scaler || b->root_scaler[t] < 0);
   }
   if (!e->bc_fast) e->bc_pat[T] = npat;
-  static const bool no_klane = BPA_EXP_SWITCH("BPA_KLANE_V1") != nullptr || BPA_EXP_SWITCH("BPA_NO_KLANE") != nullptr;
-  if (!all_jc && (!all_kl || no_klane)) return 1;
+  if (!all_jc && !all_kl) return 1;
   if (maxops > 255) return 1;                    // StepRec counts a locus's updates in a byte
   const unsigned nmat = b->mat_off ? b->mat_off[T] : 0;
   const unsigned units = 1 + std::max(maxops, 3u);
@@ -1790,37 +1734,19 @@ static int batch_end_packed(bpa_engine * e, const bpa_batch_t * b, double * lnl,
 
 static int batch_evaluate_packed(bpa_engine * e, const bpa_batch_t * b, double * lnl, bool & handled)
 {
-  static const bool prof = BPA_EXP_SWITCH("BPA_PLAN_PROF") != nullptr;       // section timers (stderr, every 130 calls)
-  static double pt[3] = {0, 0, 0}; static unsigned pcalls = 0;
   std::lock_guard<std::recursive_mutex> lock_(e->mtx);
-  const double t_0 = prof ? batch_now() : 0;
   if (!batch_begin_packed(e, b, handled)) return 0;
   if (!handled) return 1;
-  const double t_1 = prof ? batch_now() : 0;
   (void)batch_fill_packed(e, b, 0, e->bc_T);
-  const double t_2 = prof ? batch_now() : 0;
+  const int r = batch_end_packed(e, b, lnl);
+  if (!r) return 0;
+  if (r == 2)
   {
-    const int r = batch_end_packed(e, b, lnl);
-    if (!r) return 0;
-    if (r == 2)
-    {
-      // (a batch the packing's bounds did not describe: the full pass decides — and may still take the one-image path)
-      if (!batch_begin_packed(e, b, handled, false)) return 0;
-      if (!handled) return 1;
-      (void)batch_fill_packed(e, b, 0, e->bc_T);
-      if (!batch_end_packed(e, b, lnl)) return 0;
-    }
-  }
-  if (prof)
-  {
-    const double t_3 = batch_now();
-    pt[0] += t_1 - t_0; pt[1] += t_2 - t_1; pt[2] += t_3 - t_2;
-    if (++pcalls % 130 == 0)
-    {
-      fprintf(stderr, "[bpa] batch_evaluate per call: checks %.3f ms, record image %.3f ms, upload + launch + lnL back %.3f ms\n",
-              1e3*pt[0]/130, 1e3*pt[1]/130, 1e3*pt[2]/130);
-      pt[0] = pt[1] = pt[2] = 0;
-    }
+    // (a batch the packing's bounds did not describe: the full pass decides — and may still take the one-image path)
+    if (!batch_begin_packed(e, b, handled, false)) return 0;
+    if (!handled) return 1;
+    (void)batch_fill_packed(e, b, 0, e->bc_T);
+    if (!batch_end_packed(e, b, lnl)) return 0;
   }
   return 1;
 }

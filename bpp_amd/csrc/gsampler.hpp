@@ -103,7 +103,7 @@ struct GArgs
   uint32_t tau_q; double tau_u, mix_c, mix_lnc;
   int8_t * pop_nc; double * pop_t2h;      // [MAXPOP][T] mode 4: the statistics the THETA kernel reads
   uint32_t refresh_logpr;
-  // 20-state loci (fmt20): the step as the records of the tiled kernels — partials_lnl_pipe20_kernel reads ops20[op_rng20[2 i]
+  // 20-state loci (fmt20): the step as the records of the tiled kernels — partials_lnl_wave20_kernel reads ops20[op_rng20[2 i]
   // .. op_rng20[2 i + 1]) and root20[i], pmatrix_wg2_kernel the entries mat_task20 / mat_pm20 / mat_length [i maxmat + j]
   // (task 0xffffffff: a hole) — one task per locus
   OpDev * ops20; uint32_t * op_rng20, * root20, * mat_task20, * mat_pm20;

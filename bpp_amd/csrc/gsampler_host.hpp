@@ -5,20 +5,6 @@
 // the substitution-parameter moves' device tables (every locus's frequencies | exchangeabilities | alpha, the roll-back
 // pairs, the loci's ids): made when a window width first becomes positive — the widths themselves travel with every
 // launch, so switching a move on or changing a width in mid-run (BPP's burn-in finetune adjustment) touches no state
-// BPA_S20_KERNEL=pipe: round 4's 20-state node-update kernel (a workgroup barrier per update) instead of partials_lnl_wave20_kernel (A/B)
-// BPA_S20_KERNEL=wave2: partials_lnl_wave20_kernel with two patterns per lane (tiles of 128 patterns, one wave per SIMD)
-// (the A/B forms of the 20-state node-update kernel inside the sampler: an experimental build's; the default build launches
-//  partials_lnl_wave20_kernel)
-#ifdef BPA_EXPERIMENTAL
-static unsigned gs_tile20() { static const unsigned v = (getenv("BPA_S20_KERNEL") && std::string(getenv("BPA_S20_KERNEL")) == "wave2") ? 128u : 64u; return v; }
-static bool gs_waverl() { static const bool v = getenv("BPA_S20_KERNEL") && std::string(getenv("BPA_S20_KERNEL")) == "waverl"; return v; }
-static bool gs_pipe20() { static const bool v = getenv("BPA_S20_KERNEL") && std::string(getenv("BPA_S20_KERNEL")) == "pipe"; return v; }
-#else
-static constexpr unsigned gs_tile20() { return 64u; }
-static constexpr bool gs_waverl() { return false; }
-static constexpr bool gs_pipe20() { return false; }
-#endif
-
 static int gs_subst_ready(bpa_sampler * s)
 {
   if (!(s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0) || s->g_sm.p) return 1;
@@ -162,7 +148,7 @@ static int gs_upload(bpa_sampler * s)
     for (unsigned i = 0; i < T; ++i)
     {
       tl[i] = s->loci[i]->id; tp[i] = off; off += s->loci[i]->sites;
-      for (unsigned n0 = 0; n0 < s->loci[i]->sites; n0 += gs_tile20()) { tt.push_back(i); tn.push_back(n0); }
+      for (unsigned n0 = 0; n0 < s->loci[i]->sites; n0 += 64u) { tt.push_back(i); tn.push_back(n0); }
     }
     tp[T] = off;
     s->g_ntiles = (unsigned)tt.size(); s->g_maxops = s->maxtips - 1;
@@ -235,11 +221,10 @@ static int gs_upload(bpa_sampler * s)
   s->epoch = 0; s->mix_pending = false; s->g_pend = 0;
   // part-batches (two by default) when there is enough of the packing to divide and the sampler's loci are in slot order
   s->g_split = false; s->g_forked = false; s->g_np = 1;
-  static const bool no_split = BPA_EXP_SWITCH("BPA_GS_NOSPLIT") != nullptr;
   // Two part-batches by default; THREE for a 4-state set whose packing spans >= 2 400 workgroups (round 6, config 3: 10 000 loci 231.7 ->
   // 241.1 it/s, 7 500: 287.6 -> 298.9, 5 000: 357.6 -> 362.7; below that the extra launches cost more than the overlap buys — 2 500:
   // 491.7 -> 480.1, 1 250: 592.8 -> 562.8; four parts: 191 at 10 000 loci — and 20-state sets lose with three: config 4 139.7 -> 136.1)
-  unsigned want_np = (unsigned)std::min(std::max(s->env_parts > 0 ? s->env_parts : 2, 2), (int)bpa_sampler::GPARTS);
+  unsigned want_np = 2;
   auto part_streams = [&](unsigned np) -> int
   {
     s->g_st[0] = e->stream;
@@ -251,13 +236,13 @@ static int gs_upload(bpa_sampler * s)
     if (!s->g_ev_fork) HIPCHK(hipEventCreateWithFlags(&s->g_ev_fork, hipEventDisableTiming));
     return 1;
   };
-  if (!s->g_s20 && !s->g_alljc && !no_split && e->usedata && T >= 2)
+  if (!s->g_s20 && !s->g_alljc && e->usedata && T >= 2)
   {
     bool mono = true;
     for (unsigned i = 0; i + 1 < T && mono; ++i) mono = loc[i].slot < loc[i + 1].slot;
     auto block_of = [&](uint32_t slot) { return (unsigned)(std::upper_bound(e->h_blk_slot_off.begin(), e->h_blk_slot_off.end(), slot) - e->h_blk_slot_off.begin()) - 1u; };
     const unsigned b_lo = block_of(loc[0].slot), b_hi = block_of(loc[T - 1].slot) + 1u, span = b_hi - b_lo;
-    if (s->env_parts <= 0 && span >= 2400u) want_np = 3;
+    if (span >= 2400u) want_np = 3;
     if (mono && span >= 48u*want_np)
     {
       // part p starts with the workgroup of the packing that holds locus p T / np
@@ -281,7 +266,7 @@ static int gs_upload(bpa_sampler * s)
   }
   // 20-state sets: parts of the loci (the step's records are per locus, the tiles in locus order): the proposal, P-matrix
   // and sum launches of one part — latency, 70 us of a 385 us step on config 4 — run under the others' node updates
-  if (s->g_s20 && !no_split && e->usedata && T >= 64u*want_np)
+  if (s->g_s20 && e->usedata && T >= 64u*want_np)
   {
     if (!part_streams(want_np)) return 0;
     s->g_split = true; s->g_np = want_np;
@@ -290,7 +275,7 @@ static int gs_upload(bpa_sampler * s)
     for (unsigned i = 0; i < T; ++i)
     {
       if (p < want_np && i == (unsigned)((size_t)T*p/want_np)) { s->g_pi[p] = i; s->g_pt[p] = nt; s->g_ps[p] = 0; s->g_pb[p] = 0; ++p; }
-      nt += (s->loci[i]->sites + gs_tile20() - 1u)/gs_tile20();
+      nt += (s->loci[i]->sites + 63u)/64u;       // (tiles of 64 patterns: partials_lnl_wave20_kernel)
     }
     s->g_pi[want_np] = T; s->g_pt[want_np] = nt;
   }
@@ -302,24 +287,17 @@ static int gs_upload(bpa_sampler * s)
 // the program's THETA / TAU / MIX, decided on the host (BPP's proposal kernel + bpa_sampler_set_program_moves + a theta prior + a theta to move)
 static bool gs_prog(const bpa_sampler * s) { return s->kernel_bpp && s->sp.program_moves && s->sp.theta_alpha > 0 && s->sp.npop > s->sp.S; }
 
-// BPA_GS_FUSEA=1: the eigensystem refresh and the P-matrix phase inside the node-update launch (step_s4_klane kernels with
-// FUSE_A).  Rounds 4's default for sets of up to 1 536 workgroups of the packing (config 3, 1 250 loci: 546 -> 567 it/s; slower
-// above: 10 000 loci 189 -> 173); since round 5 the proposal's lane groups fill the step's P-matrices (gs_step: fuse_pm), which
-// is ahead at every size (1 250 loci 507 -> 513 it/s, 2 500: 408 -> 423, 10 000: 194 -> 207), so this is a switch only
-static bool gs_fuse_a(const bpa_sampler * s)
-{
-  return !s->g_alljc && !s->g_s20 && s->env_fusea == 1;         // (read at the sampler's creation: this runs per launch)
-}
-// Round 6: a step whose P-matrices the proposal kernel could NOT fill — a substitution-parameter step (every matrix of every locus
+// The eigensystem refresh and the P-matrix phase inside the node-update launch (step_s4_klane kernels with FUSE_A).  The
+// proposal's lane groups fill an ordinary step's P-matrices (gs_step: fuse_pm), which is ahead at every size (1 250 loci 507 ->
+// 513 it/s, 2 500: 408 -> 423, 10 000: 194 -> 207).  A step whose P-matrices the proposal kernel could NOT fill — a substitution-parameter step (every matrix of every locus
 // from a moved parameter block, the eigensystems first) and the step after one (the rejected proposals rolled back) — was four
 // launches: proposal, eigen_kernel, pmatrix_s4_dense_kernel, node updates.  On a small set (a strong-scaling rank's share: every
 // launch ~15-25 us whatever it does, an iteration a chain of them) the FUSE_A form of the node-update kernel takes the middle two
 // inside: two launches.  Sets of more than 1 536 workgroups of the packing keep the separate launches (the fused kernel's registers
-// cost it a wave per SIMD: round 4's threshold).  BPA_GS_FUSEA=0: never.
+// cost it a wave per SIMD: round 4's threshold).
 static bool gs_fuse_a_step(const bpa_sampler * s)
 {
-  if (gs_fuse_a(s)) return true;
-  return s->env_fusea != 0 && !s->g_alljc && !s->g_s20 && !s->g_pm_fused && s->eng->pack_blocks <= 1536u;
+  return !s->g_alljc && !s->g_s20 && !s->g_pm_fused && s->eng->pack_blocks <= 1536u;
 }
 
 static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u = 0, double mix_c = 1.0, double mix_lnc = 0, double tau_w = 0)
@@ -353,7 +331,7 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   // ... unless the launch is the one-lane kernel (settle, start-up, the parameter moves) on 4-state loci whose eigensystems are
   // level now: its lanes then refresh what they write themselves (GArgs::fuse_eigen, round 6) and nothing is left stale
   const bool touches_eigen = mode == 6 || mode == 7 || (s->g_pend == 4 && (s->g_pend_mode == 6 || s->g_pend_mode == 7));
-  a.fuse_eigen = (touches_eigen && mode >= 4 && mode != 10 && !s->g_s20 && !s->g_alljc && e->usedata && !s->g_eigen_dirty && !s->env_noeigfuse) ? 1u : 0u;
+  a.fuse_eigen = (touches_eigen && mode >= 4 && mode != 10 && !s->g_s20 && !s->g_alljc && e->usedata && !s->g_eigen_dirty) ? 1u : 0u;
   if (touches_eigen && !a.fuse_eigen) s->g_eigen_dirty = true;
   // diagnostics (BPA_GS_DIFF=1): a GAGE / GSPR step by both kernels from the same state, whatever differs is reported;
   // the run goes on with the one-lane kernel's result
@@ -370,18 +348,12 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
     else switch (a.mode) { case 0: hipLaunchKernelGGL((gsm::gstep_kernel<0, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; case 1: hipLaunchKernelGGL((gsm::gstep_kernel<1, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; \
                            case 2: hipLaunchKernelGGL((gsm::gstep_kernel<2, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; default: hipLaunchKernelGGL((gsm::gstep_kernel<3, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; } } while (0)
   static const bool gs_diff = getenv("BPA_GS_DIFF") != nullptr;
-  static const bool gs_v1 = BPA_EXP_SWITCH("BPA_GS_V1") != nullptr;
   // the step's P-matrices by the proposal's lane groups (gstep2_body) instead of a launch of their own: 4-state loci on the
-  // packing whose step launch does not make them itself (gs_fuse_a), no substitution-parameter step pending or rolled back
-  // since the eigensystems were last refreshed (BPA_GS_FUSEPM=0: the dense launch).  A pending RATE step (mode 9) does not turn
+  // packing, no substitution-parameter step pending or rolled back since the eigensystems were last refreshed.  A pending RATE step (mode 9) does not turn
   // this off: it wrote no parameter block, and the lane group reads the locus's rate after it has settled that step
-  s->g_pm_fused = false;
-  if (mode <= 3 && !gs_v1 && !gs_diff && !s->g_s20 && !s->g_alljc && e->usedata && (s->g_pend != 4 || s->g_pend_mode == 9) && !s->g_eigen_dirty && !gs_fuse_a(s))
-  {
-    s->g_pm_fused = s->env_fusepm;
-  }
+  s->g_pm_fused = mode <= 3 && !gs_diff && !s->g_s20 && !s->g_alljc && e->usedata && (s->g_pend != 4 || s->g_pend_mode == 9) && !s->g_eigen_dirty;
   a.fuse_pm = s->g_pm_fused ? 1u : 0u;
-  if (s->kernel_bpp && mode <= 3 && (gs_diff || gs_v1)) return fail("bpa_sampler: BPP's proposal kernel has no one-lane form (BPA_GS_DIFF / BPA_GS_V1 are the uniform kernel's diagnostics)");
+  if (s->kernel_bpp && mode <= 3 && gs_diff) return fail("bpa_sampler: BPP's proposal kernel has no one-lane form (BPA_GS_DIFF is the uniform kernel's diagnostic)");
   if (gs_diff && mode <= 3 && !s->g_forked)
   {
     const unsigned n = s->nloci;
@@ -486,9 +458,8 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
     a.i0 = s->g_forked ? s->g_pi[h] : 0u; a.iend = s->g_forked ? s->g_pi[h + 1] : s->nloci;
     const dim3 grid((a.iend - a.i0 + gsm::GBS - 1)/gsm::GBS), block(gsm::GBS);
     hipStream_t st = h ? s->g_st[h] : e->stream;
-    // GAGE / GSPR / TAU / MIX: a group of lanes per locus (gsampler2.hpp; BPA_GS_V1=1: the one-lane-per-locus kernel); HRDT has
-    // the lane-group form only
-    if ((a.mode <= 3 && !gs_v1) || a.mode == 10)
+    // GAGE / GSPR / TAU / MIX / HRDT: a group of lanes per locus (gsampler2.hpp)
+    if (a.mode <= 3 || a.mode == 10)
     {
       const unsigned lpw = s->maxtips <= 8 ? 4u : 2u;
       GS2_LAUNCH(dim3((a.iend - a.i0 + lpw - 1)/lpw), st);
@@ -506,13 +477,6 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
     s->launches++;
   }
   HIPCHK(hipGetLastError());
-  static const bool dbg_sync = BPA_EXP_SWITCH("BPA_GS_SYNC") != nullptr;        // diagnostics: wait for every launch and say which it was
-  if (dbg_sync)
-  {
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (s->g_forked) for (unsigned p = 1; p < s->g_np; ++p) HIPCHK(hipStreamSynchronize(s->g_st[p]));
-    fprintf(stderr, "[gs] step mode %u k %u pend %u done\n", mode, k, a.pend);
-  }
 #ifdef GS2_PROF
   if (mode <= 1)
   {
@@ -536,9 +500,7 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
 // stored — no step of a sampler reads a root's buffer (the root term is taken from registers in the same launch; a node that
 // stops being the root is recomputed by the step that moves it).  What else may read the loci's buffers (the single-locus API,
 // a plan, bpa_batch_evaluate) comes after a download, which recomputes every buffer in place first (gs_download).
-// BPA_GS_ROOTSTORE=1: every parent stored (A/B).
-static uint32_t gs_skip_root_flag(const bpa_sampler * s) { return s->env_rootstore ? 0u : 2048u; }
-static uint32_t gs_root_flag(const bpa_sampler * s) { return s->g_level_eval ? 0u : gs_skip_root_flag(s); }
+static uint32_t gs_root_flag(const bpa_sampler * s) { return s->g_level_eval ? 0u : 2048u; }
 // ... and until that download the loci say so: a single-locus call, a plan or a batch on one of them fails (engine.hip:
 // roots_level) instead of reading a root buffer no step has written.  Marked once per run of steps, cleared by gs_level_roots.
 static void gs_mark_roots(bpa_sampler * s, bool stale)
@@ -553,7 +515,7 @@ static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci ste
 {
   bpa_engine * e = s->eng;
   if (!e->usedata) return 1;                       // lnL = 0 for every locus (the buffer was zeroed): the MSC prior
-  if (!s->g_alljc && !s->g_level_eval && gs_skip_root_flag(s) && !s->g_root_stale) gs_mark_roots(s, true);
+  if (!s->g_alljc && !s->g_level_eval && !s->g_root_stale) gs_mark_roots(s, true);
   if (s->g_s20)
   {
     // amino-acid loci: fresh P-matrices (pmatrix_wg2_kernel, one workgroup per entry, holes return at once), the tiled
@@ -573,22 +535,9 @@ static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci ste
       k0 = t.e0; k1 = t.e1;
     }
     const size_t lds20 = ((size_t)4*s->g_rmax*400 + (size_t)s->g_rmax*64)*sizeof(double);
-    // BPA_S20_SUM_FUSED=1: the per-locus sum inside the node-update kernel (its last tile of a locus adds the terms up; one launch
-    // fewer per step and half).  Measured on config 4 and NOT the default: 119 it/s against 132 with lnl_reduce_wave_kernel as
-    // a launch of its own — the arriving wave must drain its CLV stores before its arrival atomic, holding the workgroup's
-    // registers and LDS meanwhile, and the last tile adds alone; with an agent-scope release fence instead of write-through
-    // terms: 72 it/s (the fence writes back the XCD's whole L2, i.e. the CLV planes just stored)
-    static const bool sum_fused = BPA_EXP_SWITCH("BPA_S20_SUM_FUSED") != nullptr;
-    const bool fuse_sum = sum_fused && !gs_pipe20() && gs_tile20() == 64u;
-    if (fuse_sum && !s->g_arrive.p)
-    {
-      if (!s->g_arrive.reserve(s->nloci)) return fail("out of device memory (arrival counters)");
-      HIPCHK(hipMemsetAsync(s->g_arrive.p, 0, (size_t)s->nloci*sizeof(uint32_t), e->stream));
-    }
-    d.tile_arrive = s->g_arrive.p;
-    const uint32_t fsum = fuse_sum ? 512u : 0u;
-    // the step's P-matrices: one workgroup per locus (its entries are adjacent in the step image), BPA_S20_PMGROUP=0: per entry
-    const bool pm_group = s->env_pmgroup;
+    // (the per-locus sum is lnl_reduce_wave_kernel, a launch of its own: summed inside the node-update kernel by a locus's
+    //  last tile it measured 119 it/s against 132 on config 4)
+    // the step's P-matrices: one workgroup per locus (its entries are adjacent in the step image)
     if (s->g_forked)
     {
       for (unsigned h = 0; h < s->g_np; ++h)
@@ -597,38 +546,24 @@ static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci ste
         hipStream_t st = h ? s->g_st[h] : e->stream;
         d.ent0 = i0*s->g_maxmat;
         d.flags = 1u | 256u;
-        if (pm_group) hipLaunchKernelGGL(pmatrix_wg2_group_kernel<20>, dim3(i1 - i0), dim3(256), 0, st, d, s->g_maxmat);
-        else hipLaunchKernelGGL(pmatrix_wg2_kernel<20>, dim3((i1 - i0)*s->g_maxmat), dim3(256), 0, st, d);
+        hipLaunchKernelGGL(pmatrix_wg2_group_kernel<20>, dim3(i1 - i0), dim3(256), 0, st, d, s->g_maxmat);
         d.blk0 = t0;
-        d.flags = 4u | 64u | 256u | fsum | gs_root_flag(s);
-#ifdef BPA_EXPERIMENTAL
-        if (gs_pipe20()) hipExtLaunchKernelGGL((partials_lnl_pipe20_kernel<20, true, 2>), dim3(t1 - t0), dim3(64*s->g_rmax), lds20, st, h ? nullptr : k0, h ? nullptr : k1, 0, d);
-        else if (gs_tile20() == 128u) hipExtLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 1, 2>), dim3(t1 - t0), dim3(64*s->g_rmax), lds20 + (size_t)s->g_rmax*64*sizeof(double), st, h ? nullptr : k0, h ? nullptr : k1, 0, d);
-        else if (gs_waverl()) hipExtLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 2, 1, true>), dim3(t1 - t0), dim3(64*s->g_rmax), lds20, st, h ? nullptr : k0, h ? nullptr : k1, 0, d);
-        else
-#endif
+        d.flags = 4u | 64u | 256u | gs_root_flag(s);
         hipExtLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 2>), dim3(t1 - t0), dim3(64*s->g_rmax), lds20, st, h ? nullptr : k0, h ? nullptr : k1, 0, d);
         d.blk0 = i0;
-        if (!fuse_sum) hipLaunchKernelGGL(lnl_reduce_wave_kernel, dim3(i1 - i0), dim3(64), 0, st, d);
+        hipLaunchKernelGGL(lnl_reduce_wave_kernel, dim3(i1 - i0), dim3(64), 0, st, d);
       }
       HIPCHK(hipGetLastError());
-      s->launches += (fuse_sum ? 2 : 3)*s->g_np; s->g_evals += s->g_np;
+      s->launches += 3*s->g_np; s->g_evals += s->g_np;
       return 1;
     }
     d.flags = 1u;
-    if (pm_group) hipLaunchKernelGGL(pmatrix_wg2_group_kernel<20>, dim3(s->nloci), dim3(256), 0, e->stream, d, s->g_maxmat);
-    else hipLaunchKernelGGL(pmatrix_wg2_kernel<20>, dim3(d.nmat), dim3(256), 0, e->stream, d);
-    d.flags = 4u | 64u | fsum | gs_root_flag(s);
-#ifdef BPA_EXPERIMENTAL
-    if (gs_pipe20()) hipExtLaunchKernelGGL((partials_lnl_pipe20_kernel<20, true, 2>), dim3(s->g_ntiles), dim3(64*s->g_rmax), lds20, e->stream, k0, k1, 0, d);
-    else if (gs_tile20() == 128u) hipExtLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 1, 2>), dim3(s->g_ntiles), dim3(64*s->g_rmax), lds20 + (size_t)s->g_rmax*64*sizeof(double), e->stream, k0, k1, 0, d);
-    else if (gs_waverl()) hipExtLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 2, 1, true>), dim3(s->g_ntiles), dim3(64*s->g_rmax), lds20, e->stream, k0, k1, 0, d);
-    else
-#endif
+    hipLaunchKernelGGL(pmatrix_wg2_group_kernel<20>, dim3(s->nloci), dim3(256), 0, e->stream, d, s->g_maxmat);
+    d.flags = 4u | 64u | gs_root_flag(s);
     hipExtLaunchKernelGGL((partials_lnl_wave20_kernel<20, true, 2>), dim3(s->g_ntiles), dim3(64*s->g_rmax), lds20, e->stream, k0, k1, 0, d);
-    if (!fuse_sum) hipLaunchKernelGGL(lnl_reduce_wave_kernel, dim3(s->nloci), dim3(64), 0, e->stream, d);
+    hipLaunchKernelGGL(lnl_reduce_wave_kernel, dim3(s->nloci), dim3(64), 0, e->stream, d);
     HIPCHK(hipGetLastError());
-    s->launches += fuse_sum ? 2 : 3; s->g_evals++;
+    s->launches += 3; s->g_evals++;
     return 1;
   }
   const bool fuse_a = gs_fuse_a_step(s);
@@ -703,8 +638,6 @@ static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci ste
   }
   HIPCHK(hipGetLastError());
   s->g_evals++;
-  static const bool dbg_sync_v = BPA_EXP_SWITCH("BPA_GS_SYNC") != nullptr;
-  if (dbg_sync_v) { HIPCHK(hipStreamSynchronize(e->stream)); fprintf(stderr, "[gs] eval done\n"); }
   return 1;
 }
 
@@ -855,14 +788,11 @@ static int gs_prog_ready(bpa_sampler * s)
 
 // where the sum kernels of the program's moves write and how the host gets it: pinned host memory the kernel stores into
 // itself, its last store an arrival word the host polls — no copy launch, no wait for the launch to retire between the sums and
-// the host's decision (config 5: a synchronisation 25 -> 16 -> ~8 us).  BPA_GS_PINOUT=1: pinned memory + hipStreamSynchronize,
-// =0: device buffer + hipMemcpy.  A poll that sees nothing for 20 ms falls back to the stream's synchronisation (and its errors).
-static int gs_prog_mode(const bpa_sampler * s) { return s->env_pinout; }
+// the host's decision (config 5: a synchronisation 25 -> 16 -> ~8 us).  Without pinned memory: the device buffer + hipMemcpy.
+// A poll that sees nothing for 20 ms falls back to the stream's synchronisation (and its errors).
 static double * gs_prog_out(bpa_sampler * s, unsigned long long * seq)
 {
   *seq = 0;
-  const int mode = gs_prog_mode(s);
-  if (mode == 0) return s->g_progout.p;
   if (!s->gp_pin)
   {
     if (hipHostMalloc((void **)&s->gp_pin, 64*sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -875,7 +805,7 @@ static double * gs_prog_out(bpa_sampler * s, unsigned long long * seq)
     }
     std::memset(s->gp_pin, 0, 64*sizeof(double));
   }
-  if (mode == 2) *seq = ++s->gp_seq;
+  *seq = ++s->gp_seq;
   return s->gp_pin_dev;
 }
 static int gs_prog_fetch(bpa_sampler * s, const double * dev, void * host, size_t bytes, unsigned long long seq, int nflags)
@@ -1250,7 +1180,6 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
       for (unsigned k = 0; k + 2 < 2*s->maxtips; ++k)   { if (!gs_step(s, 1, k) || !gs_eval(s, 0)) return 0; }
     }
     s->sweeps++;
-    if (s->env_nomix) continue;
     if (prog)
     {
       // (a00_iterate: the first TAU's window comes before the THETA step's numbers in the global stream)

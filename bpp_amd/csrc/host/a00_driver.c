@@ -11,20 +11,11 @@
  * reaches "proposal j of locus i" in locus-major order, while "step j of every locus" — the batch the GPU
  * needs — consumes in proposal-major order; streams here are per locus for that reason.
  */
-#define _POSIX_C_SOURCE 199309L     /* clock_gettime (the A00_PROF step profile) */
-#include <time.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
 #include "bpp_amd_host.h"
-
-/* section timers of the launch loop: an experimental build's (-DBPA_EXPERIMENTAL), like the library's A/B switches (csrc/device_types.hpp) */
-#ifdef BPA_EXPERIMENTAL
-#define A00_EXP_SWITCH(name_) getenv(name_)
-#else
-#define A00_EXP_SWITCH(name_) ((const char *)0)
-#endif
 
 #define MAXN 512                          /* nodes per gene tree handled on the stack */
 
@@ -97,7 +88,6 @@ struct a00_driver
 };
 
 
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9*ts.tv_nsec; }
 
 /* the reference's buffer toggles (locus.c:24-26) */
 static void swap_clv(a00_tree_t * t, int i)
@@ -784,39 +774,21 @@ static int per_locus_step(a00_driver_t * d, int kind, int k)
   {
     struct a00_view * w = d->view + 1 + c;
     a00_step_t s; int r;
-    static int prof = -1; static double tp[5]; static unsigned calls;
-    double t0, t1, t2, t3, t4;
-    if (prof < 0) prof = A00_EXP_SWITCH("A00_PROF") != NULL;
     set_view(d, 1 + c);
-    t0 = prof ? now_s() : 0;
     {
       const int settle = w->inflight != 0; unsigned long acc;
       if (w->inflight == 1 && !d->co_wait(d->co_ctx[c], d->s_lnl, w->n)) { w->inflight = 0; set_view(d, 0); return 0; }
-      t1 = t2 = prof ? now_s() : 0;
       /* the pending decisions and the new proposals of the cohort's loci in ONE pass: a locus's decision, then its proposal */
       acc = kind ? gspr_propose(d, k, settle) : gage_propose(d, k, settle);
       if (settle) { d->proposals += w->n; d->accepted += acc; }
       w->inflight = 0;
     }
-    t3 = prof ? now_s() : 0;
     w->n = n = compact(d);
-    t4 = prof ? now_s() : 0;
     if (!n) continue;
     view_step(d, n, &s);
     d->steps++;
     if (!(r = d->co_submit(d->co_ctx[c], &s, d->s_lnl))) { set_view(d, 0); return 0; }
     w->inflight = r;                                  /* 1: in flight, 2: evaluated already (the lnL are there) */
-    if (prof)
-    {
-      const double t5 = now_s();
-      tp[0] += t1 - t0; tp[1] += t2 - t1; tp[2] += t3 - t2; tp[3] += t4 - t3; tp[4] += t5 - t4;
-      if (++calls % 260 == 0)
-      {
-        fprintf(stderr, "[a00] per cohort step: wait %.3f ms, decide %.3f, propose %.3f, compact %.3f, submit %.3f\n",
-                1e3*tp[0]/260, 1e3*tp[1]/260, 1e3*tp[2]/260, 1e3*tp[3]/260, 1e3*tp[4]/260);
-        tp[0] = tp[1] = tp[2] = tp[3] = tp[4] = 0;
-      }
-    }
   }
   set_view(d, 0);
   return 1;
@@ -1461,12 +1433,8 @@ void a00_counters(const a00_driver_t * d, unsigned long * proposals, unsigned lo
  * back-end on libbpp_amd.so: node terms -> explicit buffer indices (what locus_update_matrices
  * / locus_update_partials read off gnode_t, locus.c:2350, 2549-2569) -> one batched launch
  * ---------------------------------------------------------------------------------------- */
-/* A00_PROF=1: where a step's wall time goes (marshalling here / bpa_batch_evaluate), printed every 130 steps */
-
 static int backend_hip_run(void * vctx, const a00_step_t * s, double * lnl, int async)
 {
-  static int prof = -1; static double t_marsh = 0, t_eval = 0, t_last = 0, t_between = 0; static unsigned calls = 0;
-  const double t0 = (prof < 0 ? (prof = A00_EXP_SWITCH("A00_PROF") != NULL) : prof) ? now_s() : 0;
   a00_hip_ctx_t * c = (a00_hip_ctx_t *)vctx;
   const unsigned n = s->nloci, nbr = s->br_off[n], nnd = s->nd_off[n];
   unsigned i, j; int ok;
@@ -1505,36 +1473,18 @@ static int backend_hip_run(void * vctx, const a00_step_t * s, double * lnl, int 
   b.nloci = n; b.loci = loci; b.mat_off = s->br_off; b.mat_pmatrix = mp; b.mat_length = ml;
   b.op_off = s->nd_off; b.ops = ops; b.root_clv = rc; b.root_scaler = rs;
   {
-    const double t1 = prof ? now_s() : 0;
     /* the record image of the step: the worker threads write it, a share of the loci each (bpa_batch_fill) */
     const int how = marshal_threads > 1 ? bpa_batch_begin(c->engine, &b) : 2;
     if (how == 1)
     {
       const int parts = marshal_threads; int q;
-      static double tb[3]; static unsigned nb_;
-      const double u0 = prof ? now_s() : 0; double u1, u2;
 #pragma omp parallel for schedule(static) num_threads(marshal_threads)
       for (q = 0; q < parts; ++q)
         (void)bpa_batch_fill(c->engine, &b, (unsigned)((unsigned long long)n*(unsigned)q/(unsigned)parts), (unsigned)((unsigned long long)n*(unsigned)(q + 1)/(unsigned)parts));
-      u1 = prof ? now_s() : 0;
       ok = async ? bpa_batch_end_async(c->engine, &b) : bpa_batch_end(c->engine, &b, lnl);
-      if (prof)
-      {
-        u2 = now_s(); tb[0] += u0 - t1; tb[1] += u1 - u0; tb[2] += u2 - u1;
-        if (++nb_ % 260 == 0) { fprintf(stderr, "[a00] per batch: begin %.3f ms, fill %.3f, end %.3f\n", 1e3*tb[0]/260, 1e3*tb[1]/260, 1e3*tb[2]/260); tb[0] = tb[1] = tb[2] = 0; }
-      }
       if (ok == 2) ok = bpa_batch_evaluate(c->engine, &b, lnl) ? (async ? 2 : 1) : 0;          /* (not the one-image path after all) */
     }
     else ok = how == 2 ? (bpa_batch_evaluate(c->engine, &b, lnl) ? (async ? 2 : 1) : 0) : 0;
-    if (prof)
-    {
-      const double t2 = now_s();
-      if (t_last > 0) t_between += t0 - t_last;
-      t_marsh += t1 - t0; t_eval += t2 - t1; t_last = t2;
-      if (++calls % 130 == 0)
-        fprintf(stderr, "[a00] per step: driver %.3f ms, marshalling %.3f ms, bpa_batch_evaluate %.3f ms\n",
-                1e3*t_between/calls, 1e3*t_marsh/calls, 1e3*t_eval/calls);
-    }
   }
   free(loci); free(mp); free(ml); free(ops); free(rc); free(rs);
   return ok;

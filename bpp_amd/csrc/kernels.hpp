@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(BPA_BLOCK) partials_lnl_s4_kernel(const PlanDe
 
 // ============================================================ K1+K2, generic S ==
 // state-major planes: clv[((buffer*R + k)*S + s)*Np + n]; one lane = one pattern.
-template <int S, typename CODE, bool NTL = false>
+template <int S, typename CODE>
 __device__ __forceinline__ void load_childN(const LocusDev & L, uint32_t clv_index, uint32_t k,
                                             uint32_t n, double * v)
 {
@@ -271,13 +271,9 @@ __device__ __forceinline__ void load_childN(const LocusDev & L, uint32_t clv_ind
   {
     const double * p = L.clv + (((size_t)(clv_index - L.tips_n)*L.rate_cats + k)*S)*L.ld + n;
 #pragma unroll
-    for (int s = 0; s < S; ++s) v[s] = NTL ? __builtin_nontemporal_load(p + (size_t)s*L.ld) : p[(size_t)s*L.ld];
+    for (int s = 0; s < S; ++s) v[s] = p[(size_t)s*L.ld];
   }
 }
-
-#ifdef BPA_EXPERIMENTAL
-#include "experimental/kernels_s20_generic_exp.hpp"   // partials_lnl_sN_kernel (one lane per pattern, no staging)
-#endif
 
 // ============================================== K1+K2, 20 states, LDS-staged P ==
 // One workgroup = one tile of TILE consecutive patterns of ONE locus; one lane = one
@@ -439,12 +435,8 @@ __device__ __forceinline__ double dot_fma4_s(cdbl4_p row, const double * v)     
   return (a0 + a1) + (a2 + a3);
 }
 
-#ifdef BPA_EXPERIMENTAL
-#include "experimental/kernels_s20_pipe_exp.hpp"      // partials_lnl_pipe20_kernel (rounds 2-4's default)
-#endif
-
 // ================================== K1+K2, 20 states, waves on their own (default since round 5) ==
-// partials_lnl_pipe20_kernel with what still ran in series taken apart.  In that kernel a tile's four waves (one per rate
+// partials_lnl_pipe20_kernel (rounds 2-4's default, since removed) with what still ran in series taken apart.  In that kernel a tile's four waves (one per rate
 // category) met at a workgroup barrier every update because the P-matrix staging was dealt out over all of them, every
 // update began by requesting its child planes and waiting for them, and ended by waiting for vmcnt(0) — i.e. for its own
 // 20 plane stores — before the barrier: load latency, arithmetic and store drain one after the other, on all four SIMDs at
@@ -488,14 +480,14 @@ __device__ __forceinline__ void stage_pmats_wave(double * s_dst, const double * 
 // ~190 us of the launch's 320 (SQ_LDS_IDX_ACTIVE agrees), against ~100 us of FP64 issue.  Two patterns per lane at one wave per
 // SIMD (the registers of two: 512 per lane) halve the reads per pattern; the wave's latency cover is the requests-ahead above.
 template <bool COHERENT = false> __device__ __forceinline__ void lnl_reduce_wave(const PlanDev & P, const uint32_t t, const uint32_t lane);
-template <int S, bool NTA = false, int OCC = 2, int PP = 1, bool RL = false>
+template <int S, bool NTA = false, int OCC = 2, int PP = 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
 partials_lnl_wave20_kernel(const PlanDev P)
 {
   extern __shared__ __attribute__((aligned(16))) double s_p[];      // [R waves][2 buffers][2 children][S][S], then [PP][R][64] scratch
   constexpr uint32_t SS = S*S;
   static_assert(S == 20 && (PP == 1 || PP == 2), "vmcnt immediates below are written for 20 PP plane stores per update");
-  const uint32_t b = ((P.flags & 256u) ? P.blk0 : 0u) + ((P.flags & 32u) ? blockIdx.x : xcd_tile(blockIdx.x, gridDim.x)), lane = threadIdx.x & 63u;
+  const uint32_t b = ((P.flags & 256u) ? P.blk0 : 0u) + xcd_tile(blockIdx.x, gridDim.x), lane = threadIdx.x & 63u;
   const uint32_t k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t t = ((cu32_p)P.tile_task)[b];
   const uint32_t n_tile = ((cu32_p)P.tile_n0)[b] + lane;
@@ -692,23 +684,10 @@ partials_lnl_wave20_kernel(const PlanDev P)
           double a[PP][4];
 #pragma unroll
           for (int q = 0; q < PP; ++q) a[q][0] = a[q][1] = a[q][2] = a[q][3] = 0;
-          // RL: the row comes out of LDS with ONE read (lane l brings entry l % S) and goes to the multiply-adds as scalar
-          // operands through v_readlane — 40 LDS reads per update instead of 400 broadcast reads of two entries each, whose
-          // latency (three in flight is what the registers allow) is what the wave waits for
-          const double prow = RL ? lm[i*S + (int)(lane % S)] : 0.0;
-          const int plo = __double2loint(prow), phi = __double2hiint(prow);
 #pragma unroll
           for (int j = 0; j < S; j += 4)
           {
-            double m0, m1, m2, m3;
-            if (RL)
-            {
-              m0 = __hiloint2double(__builtin_amdgcn_readlane(phi, j), __builtin_amdgcn_readlane(plo, j));
-              m1 = __hiloint2double(__builtin_amdgcn_readlane(phi, j + 1), __builtin_amdgcn_readlane(plo, j + 1));
-              m2 = __hiloint2double(__builtin_amdgcn_readlane(phi, j + 2), __builtin_amdgcn_readlane(plo, j + 2));
-              m3 = __hiloint2double(__builtin_amdgcn_readlane(phi, j + 3), __builtin_amdgcn_readlane(plo, j + 3));
-            }
-            else { m0 = lm[i*S + j]; m1 = lm[i*S + j + 1]; m2 = lm[i*S + j + 2]; m3 = lm[i*S + j + 3]; }
+            const double m0 = lm[i*S + j], m1 = lm[i*S + j + 1], m2 = lm[i*S + j + 2], m3 = lm[i*S + j + 3];
 #pragma unroll
             for (int q = 0; q < PP; ++q)
             {
@@ -727,20 +706,10 @@ partials_lnl_wave20_kernel(const PlanDev P)
           double a[PP][4];
 #pragma unroll
           for (int q = 0; q < PP; ++q) a[q][0] = a[q][1] = a[q][2] = a[q][3] = 0;
-          const double prow = RL ? rm[i*S + (int)(lane % S)] : 0.0;
-          const int plo = __double2loint(prow), phi = __double2hiint(prow);
 #pragma unroll
           for (int j = 0; j < S; j += 4)
           {
-            double m0, m1, m2, m3;
-            if (RL)
-            {
-              m0 = __hiloint2double(__builtin_amdgcn_readlane(phi, j), __builtin_amdgcn_readlane(plo, j));
-              m1 = __hiloint2double(__builtin_amdgcn_readlane(phi, j + 1), __builtin_amdgcn_readlane(plo, j + 1));
-              m2 = __hiloint2double(__builtin_amdgcn_readlane(phi, j + 2), __builtin_amdgcn_readlane(plo, j + 2));
-              m3 = __hiloint2double(__builtin_amdgcn_readlane(phi, j + 3), __builtin_amdgcn_readlane(plo, j + 3));
-            }
-            else { m0 = rm[i*S + j]; m1 = rm[i*S + j + 1]; m2 = rm[i*S + j + 2]; m3 = rm[i*S + j + 3]; }
+            const double m0 = rm[i*S + j], m1 = rm[i*S + j + 1], m2 = rm[i*S + j + 2], m3 = rm[i*S + j + 3];
 #pragma unroll
             for (int q = 0; q < PP; ++q)
             {
@@ -901,7 +870,7 @@ partials_lnl_pipemfma20_kernel(const PlanDev P)
   constexpr int S = 20, NG = 4;
   constexpr uint32_t SS = 400;
   extern __shared__ __attribute__((aligned(16))) double s_p[];      // [2 buffers][2 children][R][S][S], then [R][64] scratch
-  const uint32_t b = (P.flags & 32u) ? blockIdx.x : xcd_tile(blockIdx.x, gridDim.x), lane = threadIdx.x & 63u, nw = blockDim.x >> 6;
+  const uint32_t b = xcd_tile(blockIdx.x, gridDim.x), lane = threadIdx.x & 63u, nw = blockDim.x >> 6;
   const uint32_t k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t t = ((cu32_p)P.tile_task)[b];
   const uint32_t n0 = ((cu32_p)P.tile_n0)[b];
@@ -1468,10 +1437,7 @@ __device__ __forceinline__ void load_vec4(const TaskRec & T, const uint32_t clv_
 }
 
 // RT > 0: compile-time rate-category count, parent CLVs forwarded in registers; RT == 0: runtime.
-// PH = phases compiled in (1 = A, 6 = B+C, 7 = all): the eigen/closed-form P-matrix code of phase A is
-// what sets the kernel's register count, so loci that take that path run A and B+C as two launches
-// and B+C keeps twice the waves in flight.
-template <int BS, int RT, int PH = 7>
+template <int BS, int RT>
 __global__ void __launch_bounds__(BS) step_s4_fused_kernel(const PlanDev P)
 {
   __shared__ double s_term[BS];
@@ -1497,7 +1463,7 @@ __global__ void __launch_bounds__(BS) step_s4_fused_kernel(const PlanDev P)
   if ((P.flags & 4u) && lane < t1 - t0) sum_rec = P.task_rec[t0 + lane];
 
   // ---- phase A: P-matrices of this workgroup's loci
-  if ((PH & 1) && (P.flags & 1u))
+  if (P.flags & 1u)
   {
     const uint32_t e0 = P.mat_off[t0], e1 = P.mat_off[t1];
     if (RT == 1)
@@ -1517,7 +1483,7 @@ __global__ void __launch_bounds__(BS) step_s4_fused_kernel(const PlanDev P)
     }
     __syncthreads();
   }
-  if (!(PH & 6) || !(P.flags & 6u)) return;
+  if (!(P.flags & 6u)) return;
 
   // ---- phase B: node updates + root term of this lane's pattern
   double term = 0;
@@ -1793,17 +1759,17 @@ __device__ __forceinline__ void expand_code(const uint32_t code, double v[4])
   v[2] = (code & 4u) ? 1.0 : 0.0; v[3] = (code & 8u) ? 1.0 : 0.0;
 }
 
-// EARLY: the step's fresh (a, b) pairs are produced by the first lanes of the workgroup (one branch each, from the
+// The step's fresh (a, b) pairs are produced by the first lanes of the workgroup (one branch each, from the
 // MatRec and branch length they fetched at kernel entry) while the update lanes are still waiting for their records,
 // handed over through LDS and written to HBM right there: the exponentials (up to six per lane before) and the old
 // tail leave the update lanes' critical path for one workgroup barrier that overlaps the record fetch.
-template <int BS, bool EARLY = true>
+template <int BS>
 __global__ void __launch_bounds__(BS) step_jc69_kernel(const PlanDev P)
 {
   constexpr int NPRE = 3;                       // node updates whose inputs are preloaded
   constexpr uint32_t NAB = 2*BS;                // fresh (a, b) pairs a workgroup can hand over through LDS
   __shared__ double s_term[BS];
-  __shared__ double2 s_ab[EARLY ? NAB : 1];
+  __shared__ double2 s_ab[NAB];
   const uint32_t b = blockIdx.x, lane = threadIdx.x;
   const uint32_t gl = b*BS + lane;
   BPA_STAMP(P, b, lane, 0);
@@ -1850,27 +1816,24 @@ __global__ void __launch_bounds__(BS) step_jc69_kernel(const PlanDev P)
 #pragma unroll
     for (int i = 0; i < 3*NPRE; ++i) ds[i] = rp[6 + i];
   }
-  const bool use_lds = EARLY && do_mats;
-  if (EARLY)
+  const bool use_lds = do_mats;
+  // K4 for this step's branches (locus.c:2342-2414), one branch per lane, while the records are in flight
+  if (have_m0)
   {
-    // K4 for this step's branches (locus.c:2342-2414), one branch per lane, while the records are in flight
-    if (have_m0)
+    double2 ab;
+    jc69_ab(m0_len, m0_rate, ab.x, ab.y);
+    *reinterpret_cast<double2 *>(m0.dst) = ab;
+    s_ab[lane] = ab;
+    for (uint32_t e = e0 + lane + BS; e < e1; e += BS)
     {
-      double2 ab;
-      jc69_ab(m0_len, m0_rate, ab.x, ab.y);
-      *reinterpret_cast<double2 *>(m0.dst) = ab;
-      s_ab[lane] = ab;
-      for (uint32_t e = e0 + lane + BS; e < e1; e += BS)
-      {
-        const MatRec m = P.mat_recs[e];
-        double2 ab2;
-        jc69_ab(P.mat_length[m.entry], m.par[par_rates(1)], ab2.x, ab2.y);
-        *reinterpret_cast<double2 *>(m.dst) = ab2;
-        if (e - e0 < NAB) s_ab[e - e0] = ab2;
-      }
+      const MatRec m = P.mat_recs[e];
+      double2 ab2;
+      jc69_ab(P.mat_length[m.entry], m.par[par_rates(1)], ab2.x, ab2.y);
+      *reinterpret_cast<double2 *>(m.dst) = ab2;
+      if (e - e0 < NAB) s_ab[e - e0] = ab2;
     }
-    if (do_mats) __syncthreads();
   }
+  if (do_mats) __syncthreads();
 
   double term = 0;
   if (work)
@@ -2059,15 +2022,6 @@ __global__ void __launch_bounds__(BS) step_jc69_kernel(const PlanDev P)
     }
   }
   BPA_STAMP(P, b, lane, 6);
-
-  // ---- tail: the step's P-matrices (their (a, b) pairs) go to HBM for later steps (K4)
-  if (!EARLY && have_m0)
-  {
-    double2 ab;
-    jc69_ab(m0_len, m0_rate, ab.x, ab.y);
-    *reinterpret_cast<double2 *>(m0.dst) = ab;
-    for (uint32_t e = e0 + lane + BS; e < e1; e += BS) pmatrix_s4_rec(P.mat_recs[e], P.mat_length, 0);
-  }
   BPA_STAMP(P, b, lane, 7);
 }
 
@@ -2449,16 +2403,14 @@ __global__ void __launch_bounds__(BS) step_jc69_v2_chain_kernel(const ChainDev C
 }
 
 // step_s4_klane_kernel on the compact records over the engine's packing (device_types.hpp; see step_jc69_v2_kernel):
-// several rate categories, any 4-state model, no scalers, no phase averaging.  WITH_A: the P-matrix phase as its own
-// launch (its eigen / closed-form code needs twice the registers of the node updates).
-// A/B switch of the staging below: flags bit 4 = every lane fetches its matrices itself (BPA_KLANE_DIRECT=1)
-__device__ __forceinline__ bool getenv_klane_direct(const PlanDev & P) { return (P.flags & 16u) != 0; }
+// several rate categories, any 4-state model, no scalers, no phase averaging.  WITH_A (the P-matrix phase alone, as the first
+// format has it: step_s4_klane_kernel<.., true>) is not instantiated here: that phase is pmatrix_s4_dense_kernel.
 
 // The P-matrix phase of the compact-record path as a DENSE grid: one lane per (fresh branch entry, rate category).
-// step_s4_klane_v2_kernel<.., true> walks the entries workgroup by workgroup of the engine's packing — a workgroup there
-// is 256 (pattern, category) lanes = two or three loci, i.e. ~40 entries for 256 lanes, and every mostly-empty wave still
-// runs the whole eigen / closed-form code: config 3 measured 27 us per step at 16 % lane use.  Nothing in this phase needs
-// the packing (entries carry their slot), so the lanes are dealt out over the entries themselves.
+// Walking the entries workgroup by workgroup of the engine's packing — a workgroup there is 256 (pattern, category) lanes =
+// two or three loci, i.e. ~40 entries for 256 lanes, and every mostly-empty wave still runs the whole eigen / closed-form
+// code — measured 27 us per step on config 3 at 16 % lane use.  Nothing in this phase needs the packing (entries carry
+// their slot), so the lanes are dealt out over the entries themselves.
 __global__ void __launch_bounds__(256) pmatrix_s4_dense_kernel(const PlanDev P, const uint32_t nent)
 {
   const uint32_t rmax = P.pad ? P.pad : 1u, i = blockIdx.x*256u + threadIdx.x;
@@ -2573,7 +2525,7 @@ step_s4_klane_v2_kernel(const PlanDev P)
     const unsigned long long fmask = __ballot(first);
     const unsigned long long odd = __ballot(grouped && S.pstride != 16u);      // (a, b) pairs of JC69 loci: nothing to stage
     const uint32_t ngroups = (uint32_t)__popcll(fmask);
-    use_lds = ngroups >= 1 && ngroups <= 4 && odd == 0 && !getenv_klane_direct(P);
+    use_lds = ngroups >= 1 && ngroups <= 4 && odd == 0;
     my_g = (uint32_t)__popcll(fmask & ((2ull << wl) - 1ull)) - 1u;
     // the group this lane stages for: its first lane holds slot, category, R and the buffer address
     const uint32_t gs = wl >> 4;
@@ -2742,12 +2694,8 @@ step_s4_klane_v2_kernel(const PlanDev P)
 // Bank conflicts: the chunk j of group g sits at position 16 g + (j ^ g) of the wave's 1-KB corner, so lanes of different
 // groups reading "their" chunk j hit different banks (v2: all four groups on the same banks whenever a 16-lane service group
 // of ds_read_b128 spans two groups).  Arithmetic, operation order and stores are v2's: same bits.
-#ifndef BPA_KLANE_OCC
-#define BPA_KLANE_OCC 4
-#endif
-#ifndef BPA_KLANE_CH
-#define BPA_KLANE_CH 2
-#endif
+static constexpr int BPA_KLANE_OCC = 4;       // waves per SIMD the register allocation of step_s4_klane_v3_kernel is held to
+static constexpr int BPA_KLANE_CH = 2;        // updates whose matrices a wave's LDS corner holds at a time
 template <int BS, bool FUSE_A = false>
 __global__ void __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(FUSE_A ? 3 : BPA_KLANE_OCC, 8)))
 step_s4_klane_v3_kernel(const PlanDev P)
@@ -2844,7 +2792,7 @@ step_s4_klane_v3_kernel(const PlanDev P)
   const bool work = has_slot && hdr.task != none && (P.flags & 6u);
   const uint32_t tips = S.tips_n;
   const unsigned long long odd = __ballot(grouped && work && S.pstride != 16u);      // (a, b) pairs of JC69 loci: nothing to stage
-  const bool use_lds = ngroups >= 1 && ngroups <= 4 && odd == 0 && !getenv_klane_direct(P);
+  const bool use_lds = ngroups >= 1 && ngroups <= 4 && odd == 0;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2853,7 +2801,7 @@ step_s4_klane_v3_kernel(const PlanDev P)
   // ---- trip 3, part 1: every update's two matrices, global -> LDS (lane 16 g + p brings chunk p ^ g of group g)
   // (the matrices of CH updates at a time — CH = 2, measured on config 3's full set: 87 us; CH = 4: 96 us with 10 spilled registers at
   //  the 128 of four waves per SIMD; everything at once, round 5's first form: 90 us, 38 KB of LDS per workgroup; five or six waves per
-  //  SIMD spill 30-86 registers: 139-199 us — tools/ab_klane_occ.sh)
+  //  SIMD spill 30-86 registers: 139-199 us)
   constexpr int CH = BPA_KLANE_CH;
   double2 * pmw = s_pmx + (size_t)wave*CH*64u;
   const double * st_pmat = nullptr;

@@ -1123,8 +1123,7 @@ struct bpa_sampler
     }
     void free() { if (p) (void)hipFree(p); p = nullptr; }
   } uc;
-  double * wg_part = nullptr; unsigned long long * stamps = nullptr; int * dec_err = nullptr;
-  bool fuse_decision = false;           // BPA_SMP_FUSE=1: the decision inside the step launch (measured: slower)
+  double * wg_part = nullptr;
   DevBuf<int8_t> pop_nc;
   smp::Species sp{};                    // species tree (host copy; the taus below are only the start values)
   bool has_theta[smp::MAXPOP] = {};     // populations that can hold a coalescence (a00_initialize)
@@ -1153,7 +1152,6 @@ struct bpa_sampler
   hipEvent_t gp_pace[4] = {nullptr, nullptr, nullptr, nullptr}; unsigned long gp_pace_n = 0;      // the end of each of the last iterations (gs_iterate: the host stays <= 2 iterations ahead)      // the program's all-loci decisions on the device (gdec_kernel): state, the sums' buffer
   unsigned long long gp_seq = 0;        // ... and the number of the launch whose arrival words the host polls (gs_prog_fetch)
   double * gp_pin = nullptr, * gp_pin_dev = nullptr;   // 64 doubles of pinned host memory the program's sum kernels write straight into (gs_prog_out)
-  DevBuf<uint32_t> g_arrive;            // 20-state loci: tiles arrived per locus (the per-locus sum inside partials_lnl_wave20_kernel)
   long long gp_k[smp::MAXPOP] = {}; double gp_T[smp::MAXPOP] = {}; bool gp_ok = false, gp_pre_valid = false; double gp_pre_window = 0;
   double gp_tau[smp::MAXPOP] = {}, gp_theta[smp::MAXPOP] = {}; bool gp_mirror = false;
   unsigned long long gp_pj[10] = {}, gp_pj_base[4] = {};     // by move type since the last bpa_sampler_adapt_finetune: tau / mix / theta window on the host, the loci's age and prune-regraft moves from the trees (base: their totals at that call)      // the host's copy of the species tree (it takes every decision)
@@ -1166,7 +1164,6 @@ struct bpa_sampler
   unsigned g_np = 1, g_pi[GPARTS + 1] = {}, g_ps[GPARTS + 1] = {}, g_pb[GPARTS + 1] = {}, g_pt[GPARTS + 1] = {};
   hipStream_t g_st[GPARTS] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t g_ev_fork = nullptr, g_ev_join[GPARTS] = {nullptr, nullptr, nullptr, nullptr};
-  int env_parts = 0;                    // BPA_GS_PARTS (experimental build): part-batches of the per-locus steps (default 2)
   DevBuf<uint8_t> g_active;
   DevBuf<uint4> g_recs;
   DevBuf<MatRec2> g_mat2;
@@ -1212,12 +1209,11 @@ struct bpa_sampler
   unsigned long g_evals = 0;            // launches of the likelihood step kernel (bpa_sampler_work reports them as `sweeps`)
   unsigned nblocks = 0, epoch = 0;
   bool logpr_stale = false;     // thetas moved since the trees' densities were stored (Args::refresh_logpr)
-  // diagnostic switches, read once at creation: BPA_SMP_DBG (bit mask, see Args::dbg), BPA_SMP_STEPS=g,q (proposal counts),
-  // BPA_SMP_TRACE (per-launch times on stderr), BPA_SMP_NOMIX (sweeps only)
-  uint32_t env_dbg = 0; int env_gage = -1, env_gspr = -1; bool env_trace = false, env_nomix = false;
-  // the generic sampler's switches (A/B and kept paths; read ONCE, at creation: nothing reads the environment on the launch path,
-  // and a test can still make samplers of either kind in one process)
-  int env_fusea = -1; bool env_noeigfuse = false, env_fusepm = true, env_pmgroup = true, env_hostdec = false, env_rootstore = false; int env_chain = -1, env_pinout = 2;
+  // diagnostic switches, read once at creation: BPA_SMP_DBG (bit mask, see Args::dbg), BPA_SMP_TRACE (per-launch times on stderr)
+  uint32_t env_dbg = 0; bool env_trace = false;
+  // the generic sampler's kept paths (read ONCE, at creation: nothing reads the environment on the launch path, and a test can
+  // still make samplers of either kind in one process)
+  bool env_hostdec = false; int env_chain = -1;
   long env_inject = 0; uint32_t env_inject_bit = 1024u; long v2_launch_no = 0;    // BPA_SMP_INJECT=k[,w]: the k-th persistent launch with all-loci steps gives up at its first wait (w: workgroup 0 alone) — tests of the run-again path
   bool mix_pending = false;             // a mixing decision taken on the device has not been applied yet
   a00_rng_t grng = 0;
@@ -1357,20 +1353,10 @@ static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const 
   }
   s->h_trees.assign(nloci, smp::Tree{});
   if (const char * dv = getenv("BPA_SMP_DBG")) s->env_dbg = (uint32_t)atoi(dv);
-  if (const char * st = BPA_EXP_SWITCH("BPA_SMP_STEPS")) { unsigned g = 0, q = 0; if (sscanf(st, "%u,%u", &g, &q) == 2) { s->env_gage = (int)g; s->env_gspr = (int)q; } }
-  s->env_trace = getenv("BPA_SMP_TRACE") != nullptr; s->env_nomix = BPA_EXP_SWITCH("BPA_SMP_NOMIX") != nullptr;
+  s->env_trace = getenv("BPA_SMP_TRACE") != nullptr;
   if (const char * inj = getenv("BPA_SMP_INJECT")) { s->env_inject = atol(inj); s->env_inject_bit = strstr(inj, ",w") ? 2048u : 1024u; }
-  s->fuse_decision = BPA_EXP_SWITCH("BPA_SMP_FUSE") != nullptr;
-  { const char * v;
-    v = BPA_EXP_SWITCH("BPA_GS_FUSEA");     s->env_fusea = v ? (v[0] == '1' ? 1 : 0) : -1;
-    v = BPA_EXP_SWITCH("BPA_GS_FUSEPM");    s->env_fusepm = !(v && v[0] == '0');
-    v = BPA_EXP_SWITCH("BPA_S20_PMGROUP");  s->env_pmgroup = !(v && v[0] == '0');
-    v = BPA_EXP_SWITCH("BPA_GS_PARTS");    s->env_parts = v ? atoi(v) : 0;
-    s->env_noeigfuse = BPA_EXP_SWITCH("BPA_GS_NOEIGFUSE") != nullptr;        // (A/B: the eigensystem refresh as a launch of its own)
-    v = getenv("BPA_GS_CHAIN");     s->env_chain = v ? (v[0] != '0' ? 1 : 0) : -1;
-    v = BPA_EXP_SWITCH("BPA_GS_PINOUT");    s->env_pinout = v ? (v[0] == '0' ? 0 : v[0] == '1' ? 1 : 2) : 2;
-    s->env_hostdec = getenv("BPA_GS_HOSTDEC") != nullptr;
-    s->env_rootstore = BPA_EXP_SWITCH("BPA_GS_ROOTSTORE") != nullptr; }
+  { const char * v = getenv("BPA_GS_CHAIN"); s->env_chain = v ? (v[0] != '0' ? 1 : 0) : -1; }
+  s->env_hostdec = getenv("BPA_GS_HOSTDEC") != nullptr;
   s->env_v1 = getenv("BPA_SMP_V1") != nullptr;
   s->sp.ft_gage = 0.004; s->sp.ft_gspr = 0.004; s->sp.ft_tau = 0.001; s->sp.ft_mix = 0.3;      // a00_create's defaults
   return s;
@@ -1395,7 +1381,7 @@ extern "C" void bpa_sampler_destroy(bpa_sampler_t * s)
     if (s->g_ev_join[p_]) { (void)hipEventDestroy(s->g_ev_join[p_]); s->g_ev_join[p_] = nullptr; }
   }
   if (s->g_ev_fork) { (void)hipEventDestroy(s->g_ev_fork); s->g_ev_fork = nullptr; }
-  s->g_t2h3.free(); s->g_progout.free(); s->g_arrive.free(); s->gp_mirror = false; s->g_dst.free(); s->g_dsum.free();
+  s->g_t2h3.free(); s->g_progout.free(); s->gp_mirror = false; s->g_dst.free(); s->g_dsum.free();
   if (s->gp_pin) { (void)hipHostFree(s->gp_pin); s->gp_pin = s->gp_pin_dev = nullptr; }
   for (auto & ev : s->gp_pace) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
   s->g_dev.free(); s->g_undo.free(); s->g_loc.free(); s->g_lnl.free(); s->g_lnlcur.free(); s->g_hast.free(); s->g_logpr.free(); s->g_delta.free(); s->g_site.free();
@@ -1526,7 +1512,7 @@ static int assign_pops_host(const bpa_sampler * s, TR & t)
   return 1;
 }
 static int gs_upload(bpa_sampler * s);
-static int sampler_launch(bpa_sampler * s, unsigned mode, double mix_c, double mix_lnc, unsigned tau_q, double tau_u, double dec_uacc);
+static int sampler_launch(bpa_sampler * s, unsigned mode, double mix_c, double mix_lnc, unsigned tau_q, double tau_u);
 static int gs_initialize(bpa_sampler * s);
 static int gs_iterate(bpa_sampler * s, unsigned iterations);
 static int gs_download(bpa_sampler * s);
@@ -1744,14 +1730,13 @@ static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & 
   // BPA_SMP_DBG & 4096: deal densely — as few workgroups as hold the waves, evenly filled (LMAX or fewer waves: one workgroup
   // of all of them), so that a few dozen loci run in pairs and hand sets over
   if (s->env_dbg & 4096u) { const unsigned g = (nwaves + LMAX - 1)/LMAX; LWAVES = std::max((nwaves + g - 1)/std::max(g, 1u), 1u); }
-  if (const char * ev = BPA_EXP_SWITCH("BPA_SMP_LWAVES")) { const unsigned v = (unsigned)std::atoi(ev); if (v >= 1 && v <= LMAX) LWAVES = v; }     // (experiments)
   const unsigned nwg = (nwaves + LWAVES - 1)/LWAVES;
   // every workgroup must be resident (they wait for each other's sums): one per CU — a workgroup takes most of a CU's LDS
   // sets change waves where a schedule is measured to win: the program's moves, four tips, 5 waves of loci — a chain of three
   // hand-overs (NOTES §17; the two step costs, in thousands of cycles, as measured there).
   // BPA_SMP_DBG & 8192: the identity schedule all the same (the A/B on one build); bits 14-15: 1 .. 3 = that many hand-overs
   smp2::Sched sched{};
-  const unsigned nprop_sweep = s->env_gage >= 0 ? (unsigned)(s->env_gage + s->env_gspr) : (unsigned)(3*s->maxtips - 3);
+  const unsigned nprop_sweep = (unsigned)(3*s->maxtips - 3);
   // the two step costs in thousands of cycles, as NOTES §17 measured them: a wave served first, the younger wave of a pair while the older runs
   constexpr double SWEEP_STEP_ALONE = 11.9, SWEEP_STEP_YOUNG = 18.1;
   bool sched_on = false;
@@ -1849,13 +1834,10 @@ static int sampler_upload(bpa_sampler * s)
       !s->pop_nc.reserve((size_t)T*smp::MAXPOP) || !s->theta_sums.reserve(smp::MAXPOP) || !s->lograt.reserve(smp::MAXN*smp::MAXN))
     return 0;
   {
-    // [nblocks] sums | [nblocks] stamps | error flag
-    const size_t nb = ((size_t)s->nblocks + 1)*8;
+    // [nblocks] sums
     s->uc.free();
-    if (!s->uc.reserve(2*nb + 64)) return fail("bpa_sampler: out of (uncached) device memory");
+    if (!s->uc.reserve(((size_t)s->nblocks + 1)*8)) return fail("bpa_sampler: out of (uncached) device memory");
     s->wg_part = reinterpret_cast<double *>(s->uc.p);
-    s->stamps = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(s->uc.p) + nb);
-    s->dec_err = reinterpret_cast<int *>(reinterpret_cast<char *>(s->uc.p) + 2*nb);
   }
   if (s->allreduce)
   {
@@ -1909,17 +1891,10 @@ static int sampler_timing_drain(bpa_sampler * s)
   return 1;
 }
 
-// dec_uacc >= 0: an all-loci step (mode 1 / 4) that takes its own decision (Args::dec_*)
-static int sampler_launch(bpa_sampler * s, unsigned mode, double mix_c, double mix_lnc = 0, unsigned tau_q = 0, double tau_u = 0,
-                          double dec_uacc = -1.0)
+static int sampler_launch(bpa_sampler * s, unsigned mode, double mix_c, double mix_lnc = 0, unsigned tau_q = 0, double tau_u = 0)
 {
   bpa_engine * e = s->eng;
-  smp::Args a{};
-  if (dec_uacc >= 0)
-  {
-    a.dec_on = 1u; a.dec_epoch = s->epoch + 1; a.dec_uacc = dec_uacc;
-    a.dec_flag = s->flag.p; a.dec_counters = s->counters.p; a.dec_taus = s->taus.p; a.dec_stamps = s->stamps; a.dec_err = s->dec_err;
-  }
+  smp::Args a{};                // (Args::dec_on stays 0: the host decides, sampler_decide)
   a.lane_rec = s->lane_rec.p; a.task_rec = s->task_rec.p; a.blk_task_off = s->blk_task_off.p;
   a.trees = s->trees.p; a.snap = s->snap.p;
   a.mix_delta = s->mix_delta.p; a.mix_flag = s->flag.p; a.mode = mode;
@@ -1933,7 +1908,6 @@ static int sampler_launch(bpa_sampler * s, unsigned mode, double mix_c, double m
   a.dbg = s->env_dbg;
   a.taus = s->taus.p; a.tau_q = tau_q; a.tau_u = tau_u; a.sp = s->sp; a.mix_lnc = mix_lnc;
   a.nsteps_gage = s->maxtips - 1; a.nsteps_gspr = 2*s->maxtips - 2; a.mix_c = mix_c;
-  if (s->env_gage >= 0) { a.nsteps_gage = (uint32_t)s->env_gage; a.nsteps_gspr = (uint32_t)s->env_gspr; }
   // the unrolled node passes of the leader's code are sized by the largest tree: 4-tip loci get their own instance
   void (*kern)(const smp::Args) = s->maxtips <= 4 ? smp::sweep_kernel<4> : smp::sweep_kernel<smp::MAXTIPS>;
   const size_t lds = (size_t)2*(s->maxtips - 1)*smp::BS*4*sizeof(double);
@@ -2290,7 +2264,7 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
   const int npop = s->sp.npop, S = s->sp.S;
   uint32_t theta_mask = 0;
   if (s->sp.theta_alpha > 0) for (int p = 0; p < npop; ++p) if (s->has_theta[p]) theta_mask |= 1u << p;
-  const bool allloci = in_kernel_allloci && !s->env_nomix;
+  const bool allloci = in_kernel_allloci;
   // exchanges of an iteration: THETA in blocks of 15 values, one per TAU, one for MIX (sweep2.hpp: exchange)
   const bool program = s->v2_prog;                                 // (k, T) per theta instead of one difference per population
   const unsigned XV = (unsigned)smp2::XV;
@@ -2324,7 +2298,6 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
       a.xshards = cs >= 1u && cs <= 4u ? 4u << cs : XSHARDS_DEFAULT;
     }
     a.nsteps_gage = s->maxtips - 1; a.nsteps_gspr = 2*s->maxtips - 2;
-    if (s->env_gage >= 0) { a.nsteps_gage = (uint32_t)s->env_gage; a.nsteps_gspr = (uint32_t)s->env_gspr; }
     a.theta_mask = theta_mask; a.do_allloci = allloci ? 1u : 0u; a.dbg = s->env_dbg;
     if (allloci && ++s->v2_launch_no == s->env_inject) a.dbg |= s->env_inject_bit;
     if (s->p2p && allloci)
@@ -2411,7 +2384,6 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
   if (s->kernel_bpp) return fail("bpa_sampler: BPP's proposal kernel runs in the persistent iteration kernel only (one GPU, or several with bpa_sampler_set_p2p)");
   // several ranks: the per-locus sweep by the persistent kernel (one launch), the all-loci steps one launch each
   const bool v2_sweep = s->v2_ok && !s->env_trace;
-  const bool fused = s->fuse_decision && !s->allreduce && !s->env_trace;      // (several GPUs: sum -> all-reduce -> decide)
   for (unsigned it = 0; it < iterations; ++it)
   {
     if (v2_sweep) { if (!sampler_iterate_v2(s, 1, false)) return 0; }
@@ -2420,7 +2392,6 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
       if (!sampler_launch(s, 0, 1.0)) return 0;                  // GAGE + GSPR of every locus (settles a pending mix first)
       s->sweeps++;
     }
-    if (s->env_nomix) continue;
     if (s->sp.theta_alpha > 0)
     {
       // THETA for every population that can hold a coalescence, from the statistics the sweep just stored: the sums and
@@ -2451,24 +2422,11 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
     for (int q = s->sp.S; q < s->sp.npop; ++q)                    // one rubber-band step per species divergence
     {
       const double uprop = a00_rndu(&s->grng), uacc_t = a00_rndu(&s->grng);
-      if (fused)
-      {
-        // the step's launch decides for itself (its last workgroup): no kernel of its own for the decision
-        if (!sampler_launch(s, 4, 1.0, 0.0, (unsigned)q, uprop, uacc_t)) return 0;
-        s->epoch++; s->mix_pending = true;
-        continue;
-      }
       if (!sampler_launch(s, 4, 1.0, 0.0, (unsigned)q, uprop)) return 0;
       if (!sampler_decide(s, uacc_t, q, -1, uprop, 1.0, 0.0)) return 0;
     }
     const double lnc = s->sp.ft_mix*(a00_rndu(&s->grng) - 0.5), c = std::exp(lnc);
     const double uacc = a00_rndu(&s->grng);
-    if (fused)
-    {
-      if (!sampler_launch(s, 1, c, lnc, 0, 0.0, uacc)) return 0;
-      s->epoch++; s->mix_pending = true;
-      continue;
-    }
     if (!sampler_launch(s, 1, c, lnc)) return 0;                 // mixing proposal of every locus
     if (!sampler_decide(s, uacc, -1, -1, 0.0, c, lnc)) return 0;
   }
@@ -2486,9 +2444,6 @@ static int sampler_download(bpa_sampler * s)
   if (!sampler_launch(s, 2, 1.0)) return 0;
   HIPCHK(hipMemcpyAsync(s->h_trees.data(), s->trees.p, s->nloci*sizeof(smp::Tree), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  int err = 0;
-  HIPCHK(hipMemcpy(&err, s->dec_err, sizeof err, hipMemcpyDeviceToHost));
-  if (err) return fail("bpa_sampler: an in-launch decision timed out waiting for a workgroup's sum (BPA_SMP_FUSE is set: unset it)");
   if (s->v2_ok)
   {
     if (s->env_dbg & 16u)
@@ -2530,7 +2485,7 @@ static int sampler_download(bpa_sampler * s)
     }
     int verr[3] = {0, 0, 0};
     HIPCHK(hipMemcpy(verr, s->v2_err.p, sizeof verr, hipMemcpyDeviceToHost));
-    err = verr[0];
+    int err = verr[0];
     if (!err && s->p2p) { HIPCHK(hipMemcpy(&err, s->p2p->d_err.p, sizeof err, hipMemcpyDeviceToHost)); if (err) return fail("bpa_sampler: the exchange between the GPUs timed out inside the persistent kernel (a rank is missing or slow; install an all-reduce callback instead)"); }
     if (err)
     {

@@ -132,10 +132,10 @@ def test_generic_sampler_on_the_anopheles_data():
     dev.close(); host.close(); eng.close()
 
 
-@pytest.mark.parametrize("nloci,iters,fuse", [(40, 3, None), (700, 2, None), (700, 2, "BPA_GS_FUSEA=1"), (700, 2, "BPA_GS_FUSEPM=0")])
+@pytest.mark.parametrize("nloci,iters,fuse", [(40, 3, None), (700, 2, None)])
 def test_generic_sampler_with_parameter_moves_equals_host_driver(nloci, iters, fuse, monkeypatch):
-    """(fuse None: the proposal's lane groups fill the step's P-matrices themselves, the eigensystems are refreshed by a launch
-    of their own; BPA_GS_FUSEA=1: both inside the node-update launch; BPA_GS_FUSEPM=0: the P-matrices as a launch of their own)
+    """(the proposal's lane groups fill the step's P-matrices themselves; the eigensystems are refreshed inside the node-update
+    launch on a small set — 40 loci — and by a launch of their own on a larger one — 700)
     the per-locus frequency / exchangeability / alpha moves (locus.c:2782-3419, prop_gamma.c:52-224) on the device —
     new values into the loci's parameter blocks, eigensystems and category rates refreshed there — against the host
     driver's param_step over libbpp_amd.so's setters: same decisions, same parameters (the category rates of a proposed
@@ -144,7 +144,6 @@ def test_generic_sampler_with_parameter_moves_equals_host_driver(nloci, iters, f
     (tests/golden/gamma_dev_sensitivity.json; the device's rates themselves: tests/test_gpu_subst_edges.py))"""
     taxa, R = 8, 4
     if fuse is not None:
-        __import__("common").skip_unless_experimental(fuse)
         monkeypatch.setenv(*fuse.split("="))
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 300, taxa, "gtr", R, seed=23)
@@ -261,13 +260,9 @@ def test_loci_of_several_kinds_in_one_sampler():
 
 @pytest.mark.parametrize("taxa,model,R,nloci,iters,subst,env", [(8, "gtr", 4, 60, 4, True, None), (8, "gtr", 4, 700, 2, True, None), (6, "lg", 4, 40, 3, False, None),
                                                                 (8, "jc69", 1, 40, 4, False, None),
-                                                                # the paths kept next to the defaults: the sums through a device buffer and a copy /
-                                                                # waited for with the stream, 20-state P-matrices a workgroup per branch entry
-                                                                (8, "gtr", 4, 60, 3, True, "BPA_GS_PINOUT=0"), (8, "gtr", 4, 60, 3, True, "BPA_GS_PINOUT=1"),
                                                                 # the all-loci decisions on the HOST (round 5's form, the trajectory reference of
                                                                 # the device's gdec_kernel, which is the default since round 6)
-                                                                (8, "gtr", 4, 60, 4, True, "BPA_GS_HOSTDEC=1"), (6, "lg", 4, 40, 3, False, "BPA_GS_HOSTDEC=1"),
-                                                                (6, "lg", 4, 40, 3, False, "BPA_S20_PMGROUP=0")])
+                                                                (8, "gtr", 4, 60, 4, True, "BPA_GS_HOSTDEC=1"), (6, "lg", 4, 40, 3, False, "BPA_GS_HOSTDEC=1")])
 def test_generic_sampler_with_the_program_s_moves_equals_host_driver(taxa, model, R, nloci, iters, subst, env, monkeypatch):
     """BPP's own iteration on the generic sampler (bpa_sampler_set_proposal_kernel(BPP) + bpa_sampler_set_program_moves): the
     per-locus proposals draw from the reference's generator with its Bactrian-Laplace windows and acceptance rule on the device
@@ -278,7 +273,6 @@ def test_generic_sampler_with_the_program_s_moves_equals_host_driver(taxa, model
     if model == "jc69":
         monkeypatch.setenv("BPA_SMP_GENERIC", "1")
     if env:
-        __import__("common").skip_unless_experimental(env)
         monkeypatch.setenv(*env.split("="))
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 300, taxa, model, R, seed=41)

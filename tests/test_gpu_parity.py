@@ -425,17 +425,16 @@ def test_against_the_reference_itself(engine, spec):
     rl.free()
 
 
-@pytest.mark.parametrize("kernel", ["waverl", "wave2", "pipe", "pipemfma", "tiled", "generic"])
+@pytest.mark.parametrize("kernel", ["pipemfma", "tiled"])
 def test_20_state_kernel_variants_are_bit_exact(engine, monkeypatch, kernel):
-    """every 20-state node-update kernel kept next to the default (BPA_S20_KERNEL: the FP64-MFMA one, the one-wave
-    fall-back of loci with more than 4 categories, the unstaged one) reproduces the reference's AVX2 summation order
-    exactly: same CLVs, scalers and lnL bits as the default pipelined kernel"""
+    """every 20-state node-update kernel kept next to the default (BPA_S20_KERNEL: the FP64-MFMA one and the one-wave
+    fall-back of loci with more than 4 categories) reproduces the reference's AVX2 summation order exactly: same CLVs,
+    scalers and lnL bits as the default kernel"""
     c = load_golden("loci.json")
     for idx in (6, 7, 11):                      # the three 20-state golden loci (11: with scaling)
         case = c[idx]
         S, R = case["states"], case["rate_cats"]
         ol, _ = __import__("test_oracle_pin").oracle_locus(case)
-        __import__("common").skip_unless_experimental(kernel)
         monkeypatch.setenv("BPA_S20_KERNEL", kernel)
         loc, gt = golden_case(engine, case)
         for nd in gt.branches():
@@ -452,6 +451,17 @@ def test_20_state_kernel_variants_are_bit_exact(engine, monkeypatch, kernel):
             loc2.set_pmatrix(nd.pmatrix_index, ol.pmat[nd.node_index])
         locus_update_partials(loc2, gt2.postorder())
         assert locus_root_loglikelihood(loc2, gt2.root) == lnl_mfma
+
+
+@pytest.mark.parametrize("kernel", ["waverl", "wave2", "pipe", "generic"])
+def test_removed_20_state_kernel_names_are_an_error(engine, monkeypatch, kernel):
+    """the names of the removed 20-state variants do not silently mean the default: the first evaluation fails and says which
+    variable asked for them"""
+    case = load_golden("loci.json")[6]                  # the smallest 20-state golden locus
+    monkeypatch.setenv("BPA_S20_KERNEL", kernel)
+    loc, gt = golden_case(engine, case)
+    with pytest.raises(bpp_amd.BpaError, match="BPA_S20_KERNEL"):
+        full_eval(loc, gt)
 
 
 @pytest.mark.parametrize("model", ["k80", "f81", "hky", "t92", "tn93", "f84"])

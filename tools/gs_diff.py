@@ -1,5 +1,5 @@
 """the generic sampler on a small set, one iteration: BPA_GS_DIFF=1 runs every GAGE / GSPR step by both proposal kernels from the
-same state and reports what differs; BPA_GS_SYNC=1 names every launch; GS2_LOCI / GS2_TAXA / GS2_MODEL size the set"""
+same state and reports what differs; GS2_LOCI / GS2_TAXA / GS2_MODEL size the set"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
