@@ -725,7 +725,7 @@ class Sampler:
 
     def set_locus_rates(self, mui):
         """the loci's mutation rates mu_i (each > 0), before initialize: every branch length is (t_parent - t_child) mu_i;
-        they stay fixed unless set_locusrate_moves switches the MUI move on (the generic sampler only)"""
+        they stay fixed unless set_locusrate_moves switches the MUI move on (the generic and the big-tree sampler)"""
         mui = _f64(mui)
         if len(mui) != self.n:
             raise ValueError("one rate per locus")
@@ -751,7 +751,7 @@ class Sampler:
 
     def set_heredity(self, h):
         """the loci's heredity scalars h_i (each > 0), before initialize: locus i's population sizes are h_i theta_p in its MSC
-        density; they stay fixed unless set_heredity_move switches the HRDT move on (the generic sampler only)"""
+        density; they stay fixed unless set_heredity_move switches the HRDT move on (the generic and the big-tree sampler)"""
         h = _f64(h)
         if len(h) != self.n:
             raise ValueError("one scalar per locus")

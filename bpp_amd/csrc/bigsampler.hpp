@@ -20,7 +20,16 @@
 // (gsm::GDecState), a locus brings its Jacobian and TAU's three T2h, and gsm::gdec_kernel decides from the sums
 // (bigsampler_host.hpp: gb_iterate).  big_step_kernel<false> is the uniform-window step as it has always been.
 //
-// Reference: gtree.c:4585 (ages), 6531 (SPR), stree.c:5512 / 4338 (tau + rubber band), prop_mixing.c:52, gtree.c:3957.
+// Per-locus scalars, with the generic sampler's contract (gsampler.hpp: GArgs) and the host driver's code (mui_step / hered_step /
+// a00_iterate of a00_driver.c), in both instantiations: a locus's heredity scalar h_i enters tree_logpr (h_i theta_p first; the
+// T2h it leaves for THETA and TAU stay unscaled, the sum kernels divide by h_i), its rate mu_i every branch length of the records.
+// Mode 9, MUI: sliding window on log mu_i from the locus's stream, every branch and every inner node evaluated again, settled
+// as pend 4 (no density term, own counters, the old rate back on rejection).  Mode 10, HRDT: h' = |h + ft_h w|, the stored tree's
+// density at h', decided inside the launch, nothing pending.  MUBAR is gsm::gmubar_kernel (bigsampler_host.hpp: gb_mubar).  Null
+// rate / scalar arrays are "all 1, no load": a sampler that never set any walks the trajectory it always did, to the bit.
+//
+// Reference: gtree.c:4585 (ages), 6531 (SPR), stree.c:5512 / 4338 (tau + rubber band), prop_mixing.c:52, gtree.c:3957,
+// stree.c:9225 (mu_i), gtree.c:8214 (heredity), locus.c:2350 (lengths x mu_i).
 #pragma once
 
 namespace gbig {
@@ -40,6 +49,8 @@ struct BTree                              // one per locus, in HBM (and its copy
   uint32_t proposals, accepted;
   uint32_t work_nupd, work_nbr, work_neval, pad_;
   uint32_t pj_gage, pj_gage_acc, pj_gspr, pj_gspr_acc;     // per-locus proposals / acceptances by move type (bpa_sampler_adapt_finetune)
+  uint32_t pj_mui, pj_mui_acc;            // the locus's rate move (mode 9): counted apart, NOT part of proposals / accepted
+  uint32_t pj_hered_acc, pad2_;           // acceptances of the heredity-scalar move (mode 10; every locus is proposed once per step: the host counts those)
   int8_t   gl[MAXPOP];                    // gene tips below each population (never changes: tips stay in their species)
 };
 
@@ -47,10 +58,21 @@ struct BArgs
 {
   BTree * trees, * undo;                  // [T] current (or proposed, while a step is being evaluated) / the state before the pending step
   uint32_t T;
-  uint32_t mode;                          // 0 GAGE k, 1 GSPR k, 2 TAU, 3 MIX, 4 settle (+ THETA statistics), 5 start-up evaluation
+  uint32_t mode;                          // 0 GAGE k, 1 GSPR k, 2 TAU, 3 MIX, 4 settle (+ THETA statistics), 5 start-up evaluation,
+                                          // 9 the locus's mutation rate mu_i (prop_locusrate_mui, stree.c:9225), 10 the locus's heredity
+                                          // scalar (prop_heredity, gtree.c:8214: decided in the launch) — gsm::GArgs's numbers
   uint32_t k;
-  uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch), 3 commit (start-up)
+  uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch), 3 commit (start-up),
+                                          // 4 per-locus decisions of a rate step (mode 9: the density did not move)
   uint32_t pend_mode;                     // pend == 1: the kind of the step being settled (0 GAGE, 1 GSPR)
+  // per-locus mutation rates and heredity scalars, with gsm::GArgs's meaning: every branch length a step writes is
+  // (t_parent - t_child) mu_i (locus.c:2350), population p's term of locus i's density is taken at h_i theta_p (gtree.c:3938-3943).
+  // mui == null / hered == null: none was ever set and the move is off, every value is 1 and no load is made
+  double * mui, * mui_old;                // [T] the rates; [T] a pending mode-9 step's old values
+  const gsm::GLrState * lr;               // the rates' mean mu_bar (mode 9 reads it)
+  double ft_mui, a_mui;
+  double * hered;                         // [T]
+  double ft_h, h_a, h_b;                  // mode 10 (HRDT): window width, the gamma(a, b) prior
   const double * lnl_new;                 // [T] lnL of the pending step's evaluation (task = locus)
   double * hast, * logpr_new;             // [T] Hastings term / proposed MSC density of the step being proposed
   double * delta;                         // [T] an all-loci step: this locus's density + Jacobian term
@@ -85,6 +107,7 @@ struct Work
   int g_a, g_p, g_s, g_g, g_popt, g_popp, g_ok;
   double g_tnew, g_tp, g_u2;
   unsigned long long g_tmask[2], g_smask[2];
+  double h, mui;                          // the locus's heredity scalar and rate (1 where the sampler has none), read once the pending step is settled
 };
 
 // ---- the host driver's helpers (a00_driver.c: swap_clv / swap_pmat, lca_pop, climb, tree_logpr_stats, install_local)
@@ -111,7 +134,8 @@ __device__ inline int climb(const Species & sp, const double * tau, int p, doubl
 }
 // gtree_logprob (gtree.c:3957) = the sum over populations, in stree->nodes order, of gtree_update_logprob_contrib; NaN if the
 // tree does not fit the species tree.  Optionally leaves the coalescence counts and T2h of every population (THETA)
-__device__ double tree_logpr(const BTree & t, const Species & sp, const double * tau, int8_t * nc_out, double * t2h_out, uint32_t stride, Work & W)
+// — the unscaled T2h: the sum kernels divide by h.  h is the locus's heredity scalar; exactly 1.0 takes the table's log(2/theta)
+__device__ double tree_logpr(const BTree & t, const Species & sp, const double * tau, int8_t * nc_out, double * t2h_out, uint32_t stride, Work & W, const double h)
 {
   int * nin = W.nin, * nc = W.nc;
   double * times = W.times, logpr = 0;
@@ -133,7 +157,7 @@ __device__ double tree_logpr(const BTree & t, const Species & sp, const double *
       }
     nc[p] = cnt;
     if (cnt >= nin[p] && cnt > 0) return __longlong_as_double(0x7ff8000000000000ll);
-    // a00_msc_t2h / a00_msc_term (bpp_amd_host.h), heredity 1
+    // a00_msc_t2h / a00_msc_term (bpp_amd_host.h)
     const double ptau = sp.parent[p] >= 0 ? tau[sp.parent[p]] : -1.0;
     int steps = cnt + (ptau >= 0 ? 1 : 0);
     if (nin[p] == steps) --steps;
@@ -146,8 +170,18 @@ __device__ double tree_logpr(const BTree & t, const Species & sp, const double *
       prev = tk;
     }
     double c = 0;
-    if (cnt) c += cnt*tau[2*MAXPOP + p];
-    if (T2h) c -= T2h/(tau[MAXPOP + p]*1.0);
+    if (h == 1.0)
+    {
+      if (cnt) c += cnt*tau[2*MAXPOP + p];
+      if (T2h) c -= T2h/(tau[MAXPOP + p]*1.0);
+    }
+    else
+    {
+      // h theta first, its logarithm in place (tree_logpr_stats of a00_driver.c; gdensity_term of gsampler.hpp)
+      const double thh = h*tau[MAXPOP + p];
+      if (cnt) c += cnt*log(2.0/thh);
+      if (T2h) c -= T2h/thh;
+    }
     logpr += c;
     if (nc_out) { nc_out[(size_t)p*stride] = (int8_t)cnt; t2h_out[(size_t)p*stride] = T2h; }
   }
@@ -268,7 +302,22 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
   if (MODE == 4)
   {
     A.active[i] = 0;
-    (void)tree_logpr(t, sp, s_tau, A.pop_nc + i, A.pop_t2h + i, A.T, W);
+    (void)tree_logpr(t, sp, s_tau, A.pop_nc + i, A.pop_t2h + i, A.T, W, W.h);
+    return;
+  }
+  if (MODE == 10)
+  {
+    // HRDT (hered_step of a00_driver.c; prop_heredity, gtree.c:8214): h' = |h + ft_h w|, the gamma(a, b) prior's ratio, the
+    // stored tree's density at h' against the stored one.  No likelihood work: decided here, nothing is left pending
+    A.active[i] = 0;
+    const double h_old = W.h, h_new = fabs(h_old + A.ft_h*rng.window());
+    if (!(h_new > 0) || !(h_new < __longlong_as_double(0x7ff0000000000000ll))) rng.skip();
+    else
+    {
+      const double lp = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W, h_new);
+      const double lnacc = ((A.h_a - 1)*log(h_new/h_old) - A.h_b*(h_new - h_old)) + (lp - t.logpr);
+      if (rng.accept(lnacc)) { t.logpr = lp; t.pj_hered_acc++; A.hered[i] = h_new; }
+    }
     return;
   }
   if (MODE == 0)
@@ -292,7 +341,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
         br[nb++] = l; br[nb++] = r; if (p >= 0) br[nb++] = v;
         nn = path_to_root(t, v, nd);
         install(t, br, nb, nd, nn);
-        A.hast[i] = 0.0; A.logpr_new[i] = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
+        A.hast[i] = 0.0; A.logpr_new[i] = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W, W.h);
         evaluate = true;
       }
     }
@@ -341,7 +390,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
           if (!dup && t.parent[bset[j]] >= 0) br[nb++] = bset[j];
         }
         install(t, br, nb, nd, nn);
-        A.hast[i] = log((double)ntg/(double)nsrc); A.logpr_new[i] = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
+        A.hast[i] = log((double)ntg/(double)nsrc); A.logpr_new[i] = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W, W.h);
         evaluate = true;
       }
     }
@@ -361,7 +410,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
       isbr[t.left[k]] = isbr[t.right[k]] = 1; if (t.parent[k] >= 0) isbr[k] = 1;
       for (int v = k; v >= 0; v = t.parent[v]) isnd[v] = 1;
     }
-    const double lp_new = prog ? tree_logpr(t, sp, s_tau, W.o_nc, W.o_t2h, 1, W) : tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
+    const double lp_new = prog ? tree_logpr(t, sp, s_tau, W.o_nc, W.o_t2h, 1, W, W.h) : tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W, W.h);
     A.logpr_new[i] = lp_new;
     if (prog)
     {
@@ -380,6 +429,25 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
       evaluate = true;
     }
   }
+  else if (MODE == 9)
+  {
+    // MUI (mui_step of a00_driver.c; mode 9 of gsm::gstep_kernel): sliding window on log mu_i, the gamma(a_mui, a_mui/mu_bar)
+    // prior's ratio; every branch at the new rate, every inner node again, no age moves and the density stays
+    const double mu_old = W.mui, l_old = log(mu_old);
+    const double l_new = reflect(l_old + A.ft_mui*rng.window(), -99.0, 99.0);
+    const double mu_new = exp(l_new);
+    A.mui_old[i] = mu_old;
+    A.mui[i] = mu_new; W.mui = mu_new;
+    A.hast[i] = (l_new - l_old) + ((A.a_mui - 1)*log(mu_new/mu_old) - (A.a_mui/A.lr->mubar)*(mu_new - mu_old));      // stree.c:9293, 9309
+    A.logpr_new[i] = t.logpr;
+    for (int k = 0; k < n; ++k)
+    {
+      if (t.left[k] >= 0) nd[nn++] = k;
+      if (t.parent[k] >= 0) br[nb++] = k;
+    }
+    install(t, br, nb, nd, nn);
+    evaluate = true;
+  }
   else
   {
     // mixing or start-up: every branch, every inner node
@@ -394,7 +462,7 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
       for (int k = 0; k < nb; ++k) swap_pmat(t, br[k]);          // start-up evaluates in place: toggle twice = no toggle
       for (int k = 0; k < nn; ++k) swap_clv(t, nd[k]);
     }
-    const double lp_new = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W);
+    const double lp_new = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, W, W.h);
     A.logpr_new[i] = lp_new;
     A.delta[i] = (prog && MODE == 3) ? (double)ninner*mix_lnc : (lp_new - t.logpr) + (double)ninner*mix_lnc;
     A.lnl_cur[i] = t.lnl;
@@ -409,11 +477,12 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
   uint32_t nm = 0;
   if (evaluate)
   {
+    const double rate_mui = W.mui;
     for (int j = 0; j < nb; ++j, ++nm)
     {
       const int x = br[j];
       A.mat_task[e0 + nm] = i; A.mat_pm[e0 + nm] = (uint32_t)t.pmat[x];
-      A.mat_length[e0 + nm] = (t.time[t.parent[x]] - t.time[x])*1.0;        // rate_mui = 1 (locus.c:2350)
+      A.mat_length[e0 + nm] = (t.time[t.parent[x]] - t.time[x])*rate_mui;        // locus.c:2350
     }
     for (int j = 0; j < nn; ++j)
     {
@@ -489,14 +558,28 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
       if (*A.flag == A.epoch) back = true;
       else { t.logpr = A.logpr_new[i]; if (A.active[i]) t.lnl = A.lnl_new[i]; }
     }
+    else if (A.pend == 4)
+    {
+      // the rate move: lnacc without a density term, its own counters; a rejection puts the old rate back
+      if (A.active[i])
+      {
+        const double lnl = A.lnl_new[i];
+        const double lnacc = (lnl - t.lnl) + A.hast[i];
+        const bool acc = stream<BPP>(t).accept(lnacc);
+        t.pj_mui++; t.pj_mui_acc += acc ? 1u : 0u;
+        if (acc) t.lnl = lnl;
+        else { back = true; A.mui[i] = A.mui_old[i]; }
+      }
+    }
     else { t.lnl = A.lnl_new[i]; t.logpr = A.logpr_new[i]; }
     s_back = back ? 1 : 0;
   }
+  if (lane == 0) { s_w.h = A.hered ? A.hered[i] : 1.0; s_w.mui = A.mui ? A.mui[i] : 1.0; }      // (after the settle: a rejected rate is back)
   __syncthreads();
   if (s_back) copy_nodes(t, A.undo[i], lane);
   __syncthreads();
   // ---- 2. THETA moved the thetas since this density was stored
-  if (lane == 0 && A.refresh_logpr) t.logpr = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, s_w);
+  if (lane == 0 && A.refresh_logpr) t.logpr = tree_logpr(t, sp, s_tau, nullptr, nullptr, 0, s_w, s_w.h);
   __syncthreads();
 
   // ---- 3. the proposed species tree of an all-loci step is this workgroup's copy of the taus
@@ -520,7 +603,7 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
     __syncthreads();
   }
   // the state a rejection comes back to (every proposing mode; a step that proposes nothing for this locus never reads it)
-  if (MODE <= 3) copy_nodes(A.undo[i], t, lane);
+  if (MODE <= 3 || MODE == 9) copy_nodes(A.undo[i], t, lane);
   __syncthreads();
   if (MODE == 1)
   {

@@ -53,6 +53,9 @@ static int gb_upload(bpa_sampler * s)
   HIPCHK(hipMemsetAsync(s->g_delta.p, 0, T*sizeof(double), e->stream));
   HIPCHK(hipMemsetAsync(s->g_active.p, 0, T, e->stream));
   if (s->allreduce) return fail("bpa_sampler: the big-tree sampler runs on one rank (a handful of loci: nothing to shard)");
+  // the rates' and the scalars' arrays where some were set or a move is on (gs_lr_ready / gs_hered_ready: the generic sampler's)
+  s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free(); s->g_hered.free();
+  if (!gs_lr_ready(s) || !gs_hered_ready(s)) return 0;
   s->epoch = 0; s->mix_pending = false; s->g_pend = 0; s->g_pend_mode = 0;
   s->uploaded = true; s->gp_mirror = false;           // (the program's moves: the decisions' state goes to the device again, gs_prog_ready)
   return 1;
@@ -72,6 +75,10 @@ static int gb_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   a.pop_nc = s->pop_nc.p; a.pop_t2h = s->pop_t2h.p;
   a.refresh_logpr = s->logpr_stale ? 1u : 0u; s->logpr_stale = false;
   a.prog = gs_prog(s) ? 1u : 0u; a.dstep = s->g_dst.p; a.t2h3 = s->g_t2h3.p;
+  a.mui = s->g_mui.p; a.mui_old = s->g_mui_old.p; a.lr = s->g_lr.p; a.ft_mui = s->g_lr_ft[0]; a.a_mui = s->g_a_mui;
+  a.hered = s->g_hered.p; a.ft_h = s->g_h_ft; a.h_a = s->g_h_a; a.h_b = s->g_h_b;
+  if (mode == 9 && !a.mui) return fail("bpa_sampler: a rate step without the rates' arrays");
+  if (mode == 10 && !a.hered) return fail("bpa_sampler: a heredity step without the scalars' array");
   a.sp = s->sp;
   // one workgroup per locus; BPP's proposal kernel is the other instantiation
   if (s->kernel_bpp) hipLaunchKernelGGL((gbig::big_step_kernel<true>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
@@ -79,7 +86,7 @@ static int gb_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   HIPCHK(hipGetLastError());
   s->launches++;
   s->g_pend_mode = mode;
-  s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : 0u;
+  s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : mode == 9 ? 4u : 0u;      // (HRDT decides in its own launch)
   return 1;
 }
 
@@ -133,7 +140,7 @@ static int gb_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
   const bool mix = q < 0;
   if (!gb_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !gb_eval(s, 1)) return 0;
   hipLaunchKernelGGL(gsm::gdec_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
-                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p, (const double *)nullptr);
+                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   s->launches++;
   s->epoch++;
@@ -141,9 +148,43 @@ static int gb_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
   return mix ? gs_dec_launch<2>(s, -1, -1) : gs_dec_launch<1>(s, q, q + 1);
 }
 
+// MUBAR (gs_mubar of gsampler_host.hpp; mubar_step of a00_driver.c): the pending rate step is settled first (the sum must see the
+// rates the loci kept), then ONE launch sums and decides — with the host's two numbers (uniform windows) or from the decisions'
+// state on the device (the program's moves: the two draws follow MIX's in the global stream, where a00_iterate puts them)
+static int gb_mubar(bpa_sampler * s)
+{
+  bpa_engine * e = s->eng;
+  if (!gb_step(s, 4)) return 0;
+  const double ft = s->g_lr_ft[1], am = s->g_a_mui, a = s->g_a_mubar, b = s->g_b_mubar;
+  if (!s->kernel_bpp)
+  {
+    const double w = a00_rndu(&s->grng) - 0.5, u = a00_rndu(&s->grng);
+    hipLaunchKernelGGL((gsm::gmubar_kernel<0>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, w, u);
+  }
+  else
+    hipLaunchKernelGGL((gsm::gmubar_kernel<1>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, &s->g_dst.p->z, ft, am, a, b, 0.0, 0.0);
+  HIPCHK(hipGetLastError());
+  s->launches++;
+  return 1;
+}
+
+// the tail of an iteration, in a00_iterate's order: the heredity scalars after MIX (method.c:5616-5621; one launch that settles
+// MIX, proposes and decides), then the loci's rates with their evaluation and the rates' mean (method.c:5745-5773).  With a fixed
+// mean MUI closes the iteration: the next launch — the next iteration's first, or the download's — settles it
+static int gb_scalars(bpa_sampler * s)
+{
+  if (s->g_h_ft > 0) { if (!gb_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
+  if (s->g_lr_ft[0] > 0) { if (!gb_step(s, 9) || !gb_eval(s, 0)) return 0; }
+  if (s->g_lr_ft[1] > 0 && (s->g_a_mubar > 0 || s->g_b_mubar > 0)) { if (!gb_mubar(s)) return 0; }
+  return 1;
+}
+
 static int gb_iterate(bpa_sampler * s, unsigned iterations)
 {
   bpa_engine * e = s->eng;
+  if (gs_lr_moves(s) && !(s->g_a_mui > 0)) return fail("bpa_sampler: the locus-rate moves need a_mui > 0");
+  if (s->g_h_ft > 0 && !(s->g_h_a > 0 && s->g_h_b > 0)) return fail("bpa_sampler: the heredity move needs a, b > 0");
+  if (!gs_lr_ready(s) || !gs_hered_ready(s)) return 0;
   s->host_current = false;
   const bool prog = gs_prog(s);
   if (s->kernel_bpp && !prog) return fail("bpa_sampler: on the big-tree sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
@@ -166,6 +207,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
       if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       HIPCHK(hipEventRecord(ev, e->stream));
       s->gp_pace_n++;
+      if (!gb_scalars(s)) return 0;
       continue;
     }
     if (s->sp.theta_alpha > 0)
@@ -175,7 +217,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
       for (int p = 0; p < s->sp.npop; ++p)
         if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
       hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                         s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)nullptr);
+                         s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)s->g_hered.p);
       HIPCHK(hipGetLastError());
       s->logpr_stale = true;
       s->launches += 1;
@@ -188,6 +230,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
     const double lnc = s->sp.ft_mix*(a00_rndu(&s->grng) - 0.5), c = std::exp(lnc);
     const double uacc = a00_rndu(&s->grng);
     if (!gb_step(s, 3, 0, 0.0, c, lnc) || !gb_eval(s, 1) || !gb_decide(s, uacc, -1, 0.0, c, lnc)) return 0;
+    if (!gb_scalars(s)) return 0;
   }
   return 1;
 }
@@ -197,6 +240,12 @@ static int gb_download(bpa_sampler * s)
   bpa_engine * e = s->eng;
   if (!gb_step(s, 4) || !gs_prog_pull(s)) return 0;
   HIPCHK(hipMemcpyAsync(s->b_trees.data(), s->b_dev.p, s->nloci*sizeof(gbig::BTree), hipMemcpyDeviceToHost, e->stream));
+  if (s->g_mui.p)
+  {
+    HIPCHK(hipMemcpyAsync(s->g_mui_host.data(), s->g_mui.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&s->g_lr_host, s->g_lr.p, sizeof(gsm::GLrState), hipMemcpyDeviceToHost, e->stream));
+  }
+  if (s->g_hered.p) HIPCHK(hipMemcpyAsync(s->g_hered_host.data(), s->g_hered.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 1;
 }

@@ -1333,13 +1333,13 @@ extern "C" void bpa_sampler_set_subst_moves(bpa_sampler_t * s, double ft_freqs, 
   s->g_ft[0] = ft_freqs; s->g_ft[1] = ft_qrates; s->g_ft[2] = ft_alpha; s->g_alpha_a = alpha_a; s->g_alpha_b = alpha_b;
 }
 
-// ---- per-locus mutation rates (include/bpp_amd.h): the generic sampler's; every other kind refuses them
+// ---- per-locus mutation rates (include/bpp_amd.h): the generic and the big-tree sampler's; every other kind refuses them
 static int lr_refuse(const bpa_sampler * s, const char * who)
 {
-  const char * kind = s->comp ? "composite" : s->big ? "big-tree" : "persistent / sweep";
-  if (!s->comp && s->generic) return 1;
+  const char * kind = s->comp ? "composite" : "persistent / sweep";
+  if (!s->comp && (s->generic || s->big)) return 1;
   static thread_local std::string msg;
-  msg = std::string(who) + ": per-locus rates and their moves run on the generic sampler only (this one is the " + kind +
+  msg = std::string(who) + ": per-locus rates and their moves run on the generic and the big-tree sampler only (this one is the " + kind +
         " sampler); BPA_SMP_GENERIC=1 makes the generic sampler take loci the LDS kernels would otherwise";
   return fail(msg.c_str());
 }
@@ -1371,7 +1371,7 @@ extern "C" int bpa_sampler_set_locusrate_moves(bpa_sampler_t * s, double ft_mui,
 {
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
   const bool on = ft_mui > 0 || ft_mubar > 0;
-  if ((s->comp || !s->generic) && !on && ft_mui == 0 && ft_mubar == 0) return 1;        // (nothing asked for)
+  if ((s->comp || !(s->generic || s->big)) && !on && ft_mui == 0 && ft_mubar == 0) return 1;        // (nothing asked for)
   if (!lr_refuse(s, "bpa_sampler_set_locusrate_moves")) return 0;
   if (!(ft_mui >= 0) || !(ft_mubar >= 0) || !(a_mubar >= 0) || !(b_mubar >= 0) || !(mubar >= 0) || !std::isfinite(mubar))
     return fail("bpa_sampler_set_locusrate_moves: widths, prior parameters and mubar are >= 0 and finite");
@@ -1394,19 +1394,20 @@ extern "C" int bpa_sampler_locusrate_counters(bpa_sampler_t * s, unsigned long p
   if (!lr_refuse(s, "bpa_sampler_locusrate_counters")) return 0;
   if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
   unsigned long p = 0, a = 0;
-  for (const auto & t : s->g_trees) { p += t.pj_mui; a += t.pj_mui_acc; }
+  if (s->big) for (const auto & t : s->b_trees) { p += t.pj_mui; a += t.pj_mui_acc; }
+  else for (const auto & t : s->g_trees) { p += t.pj_mui; a += t.pj_mui_acc; }
   if (prop) { prop[0] = p; prop[1] = (unsigned long)s->g_lr_host.nprop; }
   if (acc) { acc[0] = a; acc[1] = (unsigned long)s->g_lr_host.nacc; }
   return 1;
 }
 
-// ---- heredity scalars (include/bpp_amd.h): the generic sampler's; every other kind refuses them
+// ---- heredity scalars (include/bpp_amd.h): the generic and the big-tree sampler's; every other kind refuses them
 static int hered_refuse(const bpa_sampler * s, const char * who)
 {
-  const char * kind = s->comp ? "composite" : s->big ? "big-tree" : "persistent / sweep";
-  if (!s->comp && s->generic) return 1;
+  const char * kind = s->comp ? "composite" : "persistent / sweep";
+  if (!s->comp && (s->generic || s->big)) return 1;
   static thread_local std::string msg;
-  msg = std::string(who) + ": heredity scalars and their move run on the generic sampler only (this one is the " + kind +
+  msg = std::string(who) + ": heredity scalars and their move run on the generic and the big-tree sampler only (this one is the " + kind +
         " sampler); BPA_SMP_GENERIC=1 makes the generic sampler take loci the LDS kernels would otherwise";
   return fail(msg.c_str());
 }
@@ -1436,7 +1437,7 @@ extern "C" int bpa_sampler_get_heredity(bpa_sampler_t * s, double * h)
 extern "C" int bpa_sampler_set_heredity_move(bpa_sampler_t * s, double ft_h, double a, double b)
 {
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
-  if ((s->comp || !s->generic) && ft_h == 0) return 1;        // (nothing asked for)
+  if ((s->comp || !(s->generic || s->big)) && ft_h == 0) return 1;        // (nothing asked for)
   if (!hered_refuse(s, "bpa_sampler_set_heredity_move")) return 0;
   if (!(ft_h >= 0) || !std::isfinite(ft_h)) return fail("bpa_sampler_set_heredity_move: the width is >= 0 and finite");
   if (ft_h > 0 && (!(a > 0) || !(b > 0) || !std::isfinite(a) || !std::isfinite(b)))
@@ -1452,7 +1453,8 @@ extern "C" int bpa_sampler_heredity_counters(bpa_sampler_t * s, unsigned long * 
   if (!hered_refuse(s, "bpa_sampler_heredity_counters")) return 0;
   if (s->uploaded && !s->host_current && !sampler_download(s)) return 0;
   unsigned long a = 0;
-  for (const auto & t : s->g_trees) a += t.pj_hered_acc;
+  if (s->big) for (const auto & t : s->b_trees) a += t.pj_hered_acc;
+  else for (const auto & t : s->g_trees) a += t.pj_hered_acc;
   if (proposed) *proposed = s->g_h_prop;
   if (accepted) *accepted = a;
   return 1;

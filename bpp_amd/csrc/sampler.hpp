@@ -2371,10 +2371,10 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
   std::lock_guard<std::recursive_mutex> lock_(e->mtx);
   if (s->comp) return comp_run(s, 1, iterations);
   // the locus-rate moves decide from the sum of ONE rank's rates: refused with several ranks, before anything is launched
-  if (s->generic && (s->g_lr_ft[0] > 0 || s->g_lr_ft[1] > 0) && (s->allreduce || s->p2p))
+  if ((s->generic || s->big) && (s->g_lr_ft[0] > 0 || s->g_lr_ft[1] > 0) && (s->allreduce || s->p2p))
     return fail("bpa_sampler_iterate: the locus-rate moves run on one rank (an all-reduce callback or the mailboxes are installed: the sum of the rates over the ranks is not exchanged)");
   // the heredity move decides per locus, but its scalars enter the THETA / TAU sums the ranks exchange: one rank only, as the rates
-  if (s->generic && s->g_h_ft > 0 && (s->allreduce || s->p2p))
+  if ((s->generic || s->big) && s->g_h_ft > 0 && (s->allreduce || s->p2p))
     return fail("bpa_sampler_iterate: the heredity move runs on one rank (an all-reduce callback or the mailboxes are installed)");
   if (!sampler_upload(s)) return 0;
   s->host_current = false;

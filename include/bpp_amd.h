@@ -448,7 +448,7 @@ void bpa_sampler_set_subst_moves(bpa_sampler_t *, double ft_freqs, double ft_qra
      MUI    prop_locusrate_mui, stree.c:9225: per locus a sliding window on log mu_i (reflected into (-99, 99)), window and
             acceptance number from the locus's own stream; lnacc = delta log mu_i + (a_mui - 1) log(mu_i'/mu_i)
             - (a_mui/mubar)(mu_i' - mu_i) + delta lnL; every P-matrix and every partial of the locus again, all on the device
-            (step mode 9 of the generic sampler);
+            (step mode 9 of the generic sampler's one-lane kernel and of the big-tree sampler's big_step_kernel);
      MUBAR  prop_locusrate_mubar, stree.c:9770: ONE decision for all loci from the sum of the rates (summed and decided on
             the device), window then acceptance number from the global stream; no likelihood work.  a_mubar = b_mubar = 0:
             mubar is fixed (cfile.c:2903; the program then uses 1) — the step does not run and draws nothing.
@@ -457,8 +457,10 @@ void bpa_sampler_set_subst_moves(bpa_sampler_t *, double ft_freqs, double ft_qra
    them fixed: the program's rates from a file); widths 0 = that move is off (default: both off), changeable at any time;
    mubar > 0 sets the mean, 0 keeps the current one; counters: index 0 = MUI, 1 = MUBAR, apart from bpa_sampler_summary's
    totals.  A sampler on which none of this is called computes what it always did, to the bit.
-   The generic sampler only (BPA_SAMPLER_GENERIC; BPA_SMP_GENERIC=1 makes it take loci the LDS kernels would otherwise):
-   rates or a non-zero width on any other kind fail, as do a rate <= 0 or not finite, a_mui <= 0 while a move is on, rates
+   The generic and the big-tree sampler (BPA_SAMPLER_GENERIC, BPA_SAMPLER_BIG; BPA_SMP_GENERIC=1 makes the generic sampler take
+   loci the LDS kernels would otherwise; the big-tree sampler reads the counters off its own trees and settles a MUI step that
+   closes an iteration in the next iteration's first launch, as the generic sampler does): rates or a non-zero width on the
+   persistent / sweep and the composite samplers fail, as do a rate <= 0 or not finite, a_mui <= 0 while a move is on, rates
    after bpa_sampler_initialize, and — when bpa_sampler_iterate is called — the moves together with an all-reduce callback
    (one rank only).  Each returns 1, or 0 with bpa_last_error set.                                                        */
 int  bpa_sampler_set_locus_rates(bpa_sampler_t *, const double * mui /* [nloci] */);
@@ -474,15 +476,17 @@ int  bpa_sampler_locusrate_counters(bpa_sampler_t *, unsigned long prop[2], unsi
      HRDT   prop_heredity, gtree.c:8214, after MIX and before the substitution-parameter moves (method.c:5616-5621): per locus
             h' = |h + ft_h w|, window and acceptance number from the locus's own stream, lnacc = (a - 1) log(h'/h) - b (h' - h)
             + logpr(h') - logpr(h); an h' that is 0 or not finite is rejected.  No likelihood work: one launch per part-batch
-            (step mode 10 of the generic sampler's lane-group kernel) proposes, decides and replaces the stored density.
+            (step mode 10 of the generic sampler's lane-group kernel; of big_step_kernel on the big-tree sampler, one launch)
+            proposes, decides and replaces the stored density.
    Meanings as the host driver's a00_set_heredity / a00_get_heredity / a00_set_heredity_move / a00_heredity_counters
    (bpp_amd_host.h): scalars [nloci], each > 0 and finite, before bpa_sampler_initialize (ft_h = 0 keeps them fixed); ft_h is the
    window width (the program borrows finetune_locusrate), 0 = off (the default), a, b > 0 while it is on, changeable at any
    time; the counters are apart from bpa_sampler_summary's totals (bpa_sampler_burnin does not adapt ft_h: apply
    bpa_finetune_onestep to them).  Heredity scalars and locus rates may be on together.  A sampler on which none of this is
    called computes what it always did, to the bit.
-   The generic sampler only (BPA_SAMPLER_GENERIC; BPA_SMP_GENERIC=1 makes it take loci the LDS kernels would otherwise): scalars
-   or a non-zero width on any other kind fail (a width of 0 is "nothing asked for": 1), as do a scalar <= 0 or not finite, a or
+   The generic and the big-tree sampler (BPA_SAMPLER_GENERIC, BPA_SAMPLER_BIG; BPA_SMP_GENERIC=1 makes the generic sampler take
+   loci the LDS kernels would otherwise — autosomal, X-linked and mitochondrial loci of many sequences each are the big-tree
+   sampler's): scalars or a non-zero width on the persistent / sweep and the composite samplers fail (a width of 0 is "nothing asked for": 1), as do a scalar <= 0 or not finite, a or
    b <= 0 while the move is on, scalars after bpa_sampler_initialize, and — when bpa_sampler_iterate is called, before any
    launch — the move together with an all-reduce callback (one rank only).  Each returns 1, or 0 with bpa_last_error set.     */
 int  bpa_sampler_set_heredity(bpa_sampler_t *, const double * h /* [nloci] */);
