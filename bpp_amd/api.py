@@ -711,16 +711,21 @@ class Sampler:
         return dict(total_lnl=tot.value, proposals=p.value, accepted=a.value, launches=l.value)
 
     def set_subst_model(self, k, freqs, qrates, alpha):
-        """starting values of locus k's substitution parameters (the moves of set_subst_moves change them)"""
+        """starting values of locus k's substitution parameters (the moves of set_subst_moves change them), before initialize;
+        the generic and the big-tree sampler take them, the persistent / sweep kind refuses (its loci are JC69)"""
         _chk(lib().bpa_sampler_set_subst_model(self.h, k, _dp(_f64(freqs)), _dp(_f64(qrates)), float(alpha)))
 
     def get_subst_model(self, k):
+        """(frequencies, exchangeabilities, alpha) of locus k as the moves left them (downloads: the pending step is settled)"""
         f, q, a = np.zeros(4), np.zeros(6), C.c_double()
         _chk(lib().bpa_sampler_get_subst_model(self.h, k, _dp(f), _dp(q), C.byref(a)))
         return f, q, a.value
 
     def set_subst_moves(self, ft_freqs, ft_qrates, ft_alpha, alpha_a=1.0, alpha_b=1.0):
-        """window widths of the per-locus frequency / exchangeability / alpha moves (0: off), gamma prior of alpha"""
+        """window widths of the per-locus frequency / exchangeability / alpha moves (0: off), gamma prior of alpha.  On the
+        generic and on the big-tree sampler (there: 4-state loci with an eigendecomposition, one rank; a locus with one rate
+        category keeps its alpha); every locus's starting values first (set_subst_model); a composite forwards the widths to
+        its generic parts"""
         lib().bpa_sampler_set_subst_moves(self.h, ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b)
 
     def set_locus_rates(self, mui):

@@ -28,8 +28,18 @@
 // density at h', decided inside the launch, nothing pending.  MUBAR is gsm::gmubar_kernel (bigsampler_host.hpp: gb_mubar).  Null
 // rate / scalar arrays are "all 1, no load": a sampler that never set any walks the trajectory it always did, to the bit.
 //
+//
+// The substitution-parameter moves, with the generic sampler's contract and the host driver's param_step, in both instantiations:
+// modes 6 (base frequency k of A, C, G against T), 7 (exchangeability k against index 1) and 8 (alpha) slide a window on the
+// logarithm from the locus's stream, keep the old pair in sm_old, write mode 9's records and are settled as pend 4 — counted in
+// proposals / accepted, the old values back in the sampler's copy on rejection.  The locus's parameter block (frequencies,
+// exchangeabilities, the category rates of alpha, rate matrix 0's eigensystem) follows in big_par_kernel, which the host
+// launches after every step launch that proposed or rolled back such a move, before the step's P-matrices are taken
+// (bigsampler_host.hpp: gb_step).  The moves' code lives in instantiations of its own, big_step_kernel<BPP, true>, launched for
+// those launches alone: a sampler on which no width was ever positive launches what it always did, the same code included.
+//
 // Reference: gtree.c:4585 (ages), 6531 (SPR), stree.c:5512 / 4338 (tau + rubber band), prop_mixing.c:52, gtree.c:3957,
-// stree.c:9225 (mu_i), gtree.c:8214 (heredity), locus.c:2350 (lengths x mu_i).
+// stree.c:9225 (mu_i), gtree.c:8214 (heredity), locus.c:2350 (lengths x mu_i), locus.c:2782 / 3168, prop_gamma.c:52 (parameters).
 #pragma once
 
 namespace gbig {
@@ -59,12 +69,13 @@ struct BArgs
   BTree * trees, * undo;                  // [T] current (or proposed, while a step is being evaluated) / the state before the pending step
   uint32_t T;
   uint32_t mode;                          // 0 GAGE k, 1 GSPR k, 2 TAU, 3 MIX, 4 settle (+ THETA statistics), 5 start-up evaluation,
+                                          // 6 base frequency k, 7 exchangeability k, 8 alpha (locus.c:2782, 3168; prop_gamma.c:52),
                                           // 9 the locus's mutation rate mu_i (prop_locusrate_mui, stree.c:9225), 10 the locus's heredity
                                           // scalar (prop_heredity, gtree.c:8214: decided in the launch) — gsm::GArgs's numbers
   uint32_t k;
   uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch), 3 commit (start-up),
-                                          // 4 per-locus decisions of a rate step (mode 9: the density did not move)
-  uint32_t pend_mode;                     // pend == 1: the kind of the step being settled (0 GAGE, 1 GSPR)
+                                          // 4 per-locus decisions of a substitution-parameter or rate step (modes 6 - 9: the density did not move)
+  uint32_t pend_mode;                     // pend == 1: the kind of the step being settled (0 GAGE, 1 GSPR); pend == 4: its mode (6 - 9)
   // per-locus mutation rates and heredity scalars, with gsm::GArgs's meaning: every branch length a step writes is
   // (t_parent - t_child) mu_i (locus.c:2350), population p's term of locus i's density is taken at h_i theta_p (gtree.c:3938-3943).
   // mui == null / hered == null: none was ever set and the move is off, every value is 1 and no load is made
@@ -93,6 +104,14 @@ struct BArgs
   const gsm::GDecState * dstep;
   double * t2h3;                          // [T][3]
   Species sp;
+  // the substitution-parameter moves, with gsm::GArgs's meaning (param_step of a00_driver.c), read by the PAR instantiations
+  // only (behind everything else: the other instantiations find their arguments where they always were).  sm == null: no width
+  // was ever positive, no step of modes 6 - 8 is launched or settled
+  double * sm, * sm_old;                  // [T][11] freqs | exchangeabilities | alpha of every locus; [T][2] the pending step's old values
+  double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
+  uint8_t * par_todo;                     // [T] the components big_par_kernel owes the locus's parameter block: bit (mode - 6)
+  const LocusDev * loci; const uint32_t * ids;      // the engine's loci and the sampler's ids among them (mode 8 reads the category count)
+  uint32_t pend_k, pad_k;                 // pend == 4, modes 6 / 7: which component that step proposed
 };
 
 // lane 0's work arrays, in LDS (as private arrays they would live in scratch memory: a round trip to HBM per access)
@@ -108,6 +127,7 @@ struct Work
   double g_tnew, g_tp, g_u2;
   unsigned long long g_tmask[2], g_smask[2];
   double h, mui;                          // the locus's heredity scalar and rate (1 where the sampler has none), read once the pending step is settled
+  uint32_t par_todo;                      // components of the sampler's copy `sm` this launch moved: bit (mode - 6), a proposal or a rejected one's old values
 };
 
 // ---- the host driver's helpers (a00_driver.c: swap_clv / swap_pmat, lca_pop, climb, tree_logpr_stats, install_local)
@@ -289,7 +309,7 @@ __device__ void gspr_scan(const BTree & t, const Species & sp, Work & W, const u
 }
 
 // ---- 4. propose (gage_step / gspr_step / tau_step / mix_step / a00_initialize of a00_driver.c, one locus), then 5. the records
-template <bool BPP>
+template <bool BPP, bool PAR>
 __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const Species & sp, const double * s_tau, const uint32_t MODE,
                             const double lminf, const double lmaxf, const double tq_old, const double tq_lo, const double tq_hi,
                             const double minf, const double maxf, const double mix_c, const double mix_lnc, Work & W)
@@ -448,6 +468,48 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
     install(t, br, nb, nd, nn);
     evaluate = true;
   }
+  else if (PAR && MODE >= 6 && MODE <= 8)
+  {
+    // a substitution-parameter move (param_step of a00_driver.c; modes 6 / 7 / 8 of gsm::gstep_kernel): the new value into the
+    // sampler's copy — big_par_kernel brings the locus's parameter block level before the P-matrices are taken — then every
+    // branch, every inner node; no age moves and the density stays.  A locus with one rate category has no alpha to move: it
+    // proposes nothing and draws nothing (a00_driver.c:1187)
+    double * m = A.sm + (size_t)i*11;
+    if (!(MODE == 8 && A.loci[A.ids[i]].rate_cats < 2))
+    {
+      double hast;
+      if (MODE == 8)
+      {
+        const double a_old = m[10], la_old = log(a_old);
+        const double la_new = reflect(la_old + A.ft_alpha*rng.window(), -99.0, 99.0);
+        const double a_new = exp(la_new);
+        A.sm_old[2*i] = a_old;
+        m[10] = a_new;
+        hast = (la_new - la_old) + ((A.alpha_a - 1)*log(a_new/a_old) - A.alpha_b*(a_new - a_old));      // prop_gamma.c:72, 133
+      }
+      else
+      {
+        double * v = MODE == 6 ? m : m + 4;
+        const int j = (int)A.k, ref = MODE == 6 ? 3 : 1;                  // T / the A<->G rate (locus.c:2791, 3222)
+        const double sum = v[j] + v[ref], lo = log(1e-5), hi = log(sum);
+        const double l_old = log(v[j]);
+        const double l_new = reflect(l_old + (MODE == 6 ? A.ft_freqs : A.ft_qrates)*rng.window(), lo, hi);
+        A.sm_old[2*i] = v[j]; A.sm_old[2*i + 1] = v[ref];
+        v[j] = exp(l_new); v[ref] = sum - v[j];
+        hast = l_new - l_old;                                               // locus.c:2867, 3296
+      }
+      W.par_todo |= 1u << (MODE - 6);
+      A.hast[i] = hast;
+      A.logpr_new[i] = t.logpr;
+      for (int k = 0; k < n; ++k)
+      {
+        if (t.left[k] >= 0) nd[nn++] = k;
+        if (t.parent[k] >= 0) br[nb++] = k;
+      }
+      install(t, br, nb, nd, nn);
+      evaluate = true;
+    }
+  }
   else
   {
     // mixing or start-up: every branch, every inner node
@@ -512,7 +574,11 @@ __device__ inline void copy_nodes(BTree & dst, const BTree & src, uint32_t lane)
   if (lane == 0) { dst.root = src.root; dst.tips = src.tips; }
 }
 
-template <bool BPP = false>
+// PAR: the instantiation that carries the substitution-parameter moves — modes 6 / 7 / 8 and the settle of such a step.  The
+// host launches it for exactly those launches (gb_step); every other launch, and every launch of a sampler without the moves,
+// runs the PAR = false code, which is the code the kernel had before the moves existed (the lone lane's instruction stream is
+// where a step's time goes: 1 % of an iteration of the frogs loci was lost with the moves' code in the one kernel)
+template <bool BPP = false, bool PAR = false>
 __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
 {
   __shared__ double s_tau[3*MAXPOP];
@@ -530,7 +596,7 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
     for (uint32_t q = lane; q < sizeof(BTree)/4; q += BBS) tdst[q] = tsrc[q];
   }
   if (lane < (uint32_t)(3*MAXPOP)) s_tau[lane] = A.taus[lane];
-  if (lane == 0) s_back = 0;
+  if (lane == 0) { s_back = 0; if (PAR) s_w.par_todo = 0; }
   __syncthreads();
   const Species & sp = s_sp;
   const uint32_t MODE = A.mode;
@@ -560,15 +626,33 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
     }
     else if (A.pend == 4)
     {
-      // the rate move: lnacc without a density term, its own counters; a rejection puts the old rate back
+      // lnacc without a density term.  The rate move: its own counters, a rejection puts the old rate back.  A substitution-
+      // parameter move: counted with the tree moves (param_step of a00_driver.c), a rejection puts the old values back in the
+      // sampler's copy and leaves the component to big_par_kernel, which restores the locus's parameter block
       if (A.active[i])
       {
         const double lnl = A.lnl_new[i];
         const double lnacc = (lnl - t.lnl) + A.hast[i];
         const bool acc = stream<BPP>(t).accept(lnacc);
-        t.pj_mui++; t.pj_mui_acc += acc ? 1u : 0u;
-        if (acc) t.lnl = lnl;
-        else { back = true; A.mui[i] = A.mui_old[i]; }
+        if (!PAR || A.pend_mode == 9)
+        {
+          t.pj_mui++; t.pj_mui_acc += acc ? 1u : 0u;
+          if (acc) t.lnl = lnl;
+          else { back = true; A.mui[i] = A.mui_old[i]; }
+        }
+        else
+        {
+          t.proposals++;
+          if (acc) { t.lnl = lnl; t.accepted++; }
+          else
+          {
+            back = true;
+            double * m = A.sm + (size_t)i*11;
+            if (A.pend_mode == 8) m[10] = A.sm_old[2*i];
+            else { double * v = A.pend_mode == 6 ? m : m + 4; const int ref = A.pend_mode == 6 ? 3 : 1; v[A.pend_k] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+            s_w.par_todo |= 1u << (A.pend_mode - 6);
+          }
+        }
       }
     }
     else { t.lnl = A.lnl_new[i]; t.logpr = A.logpr_new[i]; }
@@ -603,7 +687,7 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
     __syncthreads();
   }
   // the state a rejection comes back to (every proposing mode; a step that proposes nothing for this locus never reads it)
-  if (MODE <= 3 || MODE == 9) copy_nodes(A.undo[i], t, lane);
+  if (MODE <= 3 || MODE == 9 || (PAR && MODE >= 6 && MODE <= 8)) copy_nodes(A.undo[i], t, lane);
   __syncthreads();
   if (MODE == 1)
   {
@@ -612,12 +696,62 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
     if (s_w.g_ok) gspr_scan(t, sp, s_w, lane);
     __syncthreads();
   }
-  if (lane == 0) big_propose<BPP>(A, i, t, sp, s_tau, MODE, lminf, lmaxf, tq_old, tq_lo, tq_hi, minf, maxf, mix_c, mix_lnc, s_w);
+  if (lane == 0) big_propose<BPP, PAR>(A, i, t, sp, s_tau, MODE, lminf, lmaxf, tq_old, tq_lo, tq_hi, minf, maxf, mix_c, mix_lnc, s_w);
+  if (PAR && lane == 0 && s_w.par_todo) A.par_todo[i] = (uint8_t)s_w.par_todo;
   __syncthreads();
   {
     const uint32_t * tsrc = reinterpret_cast<const uint32_t *>(&s_t);
     uint32_t * tdst = reinterpret_cast<uint32_t *>(A.trees + i);
     for (uint32_t q = lane; q < sizeof(BTree)/4; q += BBS) tdst[q] = tsrc[q];
+  }
+}
+
+// The loci's parameter blocks follow the sampler's copy `sm` (stage 4b of gsm::gstep_kernel, as a kernel of its own: the
+// incomplete-gamma loops and the 4x4 eigensystem in registers do not belong among big_step_kernel's 64 / 68 VGPRs).  One
+// workgroup per locus, lane 0 working, nothing to do where the step kernel left the locus's byte clear.  A component the step
+// kernel moved — the old values of a rejected proposal put back, a new proposal, or both in one launch — is written from `sm`,
+// whose values are final when this runs (a restored and a newly proposed component never overlap in time), with
+// gsm::write_par's statements: frequencies, exchangeabilities, or the category rates of alpha by gdev::gamma_cats
+// (prop_gamma.c:93-97); then K6 once where the rate matrix moved (update_eigen_regs<4> on rate matrix 0, the one these moves
+// write).  Same routines, same inputs, same bits as the generic sampler.  The category count is a compile-time constant of each
+// gamma_cats call: its cut points then live in registers, not in scratch memory.
+template <unsigned R> __device__ __forceinline__ void par_category_rates(double * par, const double alpha)
+{
+  double rates[8];
+  gdev::gamma_cats(alpha, R, rates);
+#pragma unroll
+  for (unsigned q = 0; q < R; ++q) par[par_rates(R) + q] = rates[q];
+}
+__global__ void __launch_bounds__(BBS) big_par_kernel(uint8_t * __restrict__ todo, const double * __restrict__ sm, const LocusDev * __restrict__ loci,
+                                                      const uint32_t * __restrict__ ids, const uint32_t T)
+{
+  const uint32_t i = blockIdx.x;
+  if (threadIdx.x || i >= T) return;
+  const uint32_t f = todo[i];
+  if (!f) return;
+  todo[i] = 0;
+  const LocusDev & L = loci[ids[i]];
+  const uint32_t R = L.rate_cats;
+  double * par = L.par;
+  const double * m = sm + (size_t)i*11;
+  if (f & 1u) gsm::write_par(par, R, 6, m);
+  if (f & 2u) gsm::write_par(par, R, 7, m);
+  if (f & 4u)
+    switch (R)
+    {
+      case 2: par_category_rates<2>(par, m[10]); break;
+      case 3: par_category_rates<3>(par, m[10]); break;
+      case 4: par_category_rates<4>(par, m[10]); break;
+      case 5: par_category_rates<5>(par, m[10]); break;
+      case 6: par_category_rates<6>(par, m[10]); break;
+      case 7: par_category_rates<7>(par, m[10]); break;
+      case 8: par_category_rates<8>(par, m[10]); break;
+      default: break;                          // (one category: the step kernel proposes no alpha)
+    }
+  if (f & 3u)
+  {
+    double * pm = par + par_matrix(R, 4, 0);
+    update_eigen_regs<4>(pm + pm_freqs(4), pm + pm_subst(4), pm + pm_evals(4), pm + pm_evecs(4), pm + pm_ievecs(4));
   }
 }
 

@@ -2,6 +2,18 @@
 // downloads.  Included at the end of sampler.hpp, after gsampler_host.hpp (whose buffers and all-loci kernels it shares).
 #pragma once
 
+// the substitution-parameter moves' tables (gs_subst_ready: the generic sampler's, with its refusals) and the loci's bytes for
+// big_par_kernel, made when a window width first becomes positive: a sampler that never set one has none of them
+static bool gb_subst_moves(const bpa_sampler * s) { return s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0; }
+static int gb_subst_ready(bpa_sampler * s)
+{
+  if (!gs_subst_ready(s)) return 0;
+  if (!s->g_sm.p || s->b_par_todo.p) return 1;
+  if (!s->b_par_todo.reserve(s->nloci)) return 0;
+  HIPCHK(hipMemsetAsync(s->b_par_todo.p, 0, s->nloci, s->eng->stream));
+  return 1;
+}
+
 static int gb_upload(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
@@ -56,7 +68,10 @@ static int gb_upload(bpa_sampler * s)
   // the rates' and the scalars' arrays where some were set or a move is on (gs_lr_ready / gs_hered_ready: the generic sampler's)
   s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free(); s->g_hered.free();
   if (!gs_lr_ready(s) || !gs_hered_ready(s)) return 0;
-  s->epoch = 0; s->mix_pending = false; s->g_pend = 0; s->g_pend_mode = 0;
+  // ... and the substitution parameters' (re-made from the host copy, as gs_upload does)
+  s->g_sm.free(); s->b_par_todo.free();
+  if (!gb_subst_ready(s)) return 0;
+  s->epoch = 0; s->mix_pending = false; s->g_pend = 0; s->g_pend_mode = 0; s->g_pend_k = 0;
   s->uploaded = true; s->gp_mirror = false;           // (the program's moves: the decisions' state goes to the device again, gs_prog_ready)
   return 1;
 }
@@ -79,14 +94,34 @@ static int gb_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   a.hered = s->g_hered.p; a.ft_h = s->g_h_ft; a.h_a = s->g_h_a; a.h_b = s->g_h_b;
   if (mode == 9 && !a.mui) return fail("bpa_sampler: a rate step without the rates' arrays");
   if (mode == 10 && !a.hered) return fail("bpa_sampler: a heredity step without the scalars' array");
+  a.sm = s->g_sm.p; a.sm_old = s->g_sm_old.p; a.pend_k = s->g_pend_k; a.par_todo = s->b_par_todo.p; a.loci = e->d_loci.p; a.ids = s->g_ids.p;
+  a.ft_freqs = s->g_ft[0]; a.ft_qrates = s->g_ft[1]; a.ft_alpha = s->g_ft[2]; a.alpha_a = s->g_alpha_a; a.alpha_b = s->g_alpha_b;
+  const bool par_step = mode >= 6 && mode <= 8, par_settled = s->g_pend == 4 && s->g_pend_mode >= 6 && s->g_pend_mode <= 8;
+  if ((par_step || par_settled) && !(a.sm && a.par_todo)) return fail("bpa_sampler: a substitution-parameter step without the moves' tables");
   a.sp = s->sp;
-  // one workgroup per locus; BPP's proposal kernel is the other instantiation
-  if (s->kernel_bpp) hipLaunchKernelGGL((gbig::big_step_kernel<true>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
+  // one workgroup per locus; BPP's proposal kernel is the other instantiation; a launch that proposes a substitution parameter
+  // or settles such a step takes the instantiation that carries the moves' code (every other launch: the code without it)
+  if (par_step || par_settled)
+  {
+    if (s->kernel_bpp) hipLaunchKernelGGL((gbig::big_step_kernel<true, true>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
+    else hipLaunchKernelGGL((gbig::big_step_kernel<false, true>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
+  }
+  else if (s->kernel_bpp) hipLaunchKernelGGL((gbig::big_step_kernel<true>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
   else hipLaunchKernelGGL((gbig::big_step_kernel<false>), dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, a);
   HIPCHK(hipGetLastError());
   s->launches++;
-  s->g_pend_mode = mode;
-  s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : mode == 9 ? 4u : 0u;      // (HRDT decides in its own launch)
+  // a launch that proposed a substitution parameter, or settled such a step (its rejections put old values back): the loci's
+  // parameter blocks and eigensystems follow the sampler's copy before anything — this step's P-matrices, a later evaluation,
+  // a download — reads them.  Loci whose byte is clear cost the launch nothing but their workgroup
+  if (par_step || par_settled)
+  {
+    hipLaunchKernelGGL(gbig::big_par_kernel, dim3(s->nloci), dim3(gbig::BBS), 0, e->stream, s->b_par_todo.p, (const double *)s->g_sm.p,
+                       (const LocusDev *)e->d_loci.p, (const uint32_t *)s->g_ids.p, (uint32_t)s->nloci);
+    HIPCHK(hipGetLastError());
+    s->launches++;
+  }
+  s->g_pend_mode = mode; s->g_pend_k = k;
+  s->g_pend = mode <= 1 ? 1u : (mode == 2 || mode == 3) ? 2u : mode == 5 ? 3u : (mode >= 6 && mode <= 9) ? 4u : 0u;      // (HRDT decides in its own launch)
   return 1;
 }
 
@@ -170,10 +205,18 @@ static int gb_mubar(bpa_sampler * s)
 
 // the tail of an iteration, in a00_iterate's order: the heredity scalars after MIX (method.c:5616-5621; one launch that settles
 // MIX, proposes and decides), then the loci's rates with their evaluation and the rates' mean (method.c:5745-5773).  With a fixed
-// mean MUI closes the iteration: the next launch — the next iteration's first, or the download's — settles it
+// mean MUI closes the iteration: the next launch — the next iteration's first, or the download's — settles it.  Between the
+// two, the substitution-parameter moves (method.c:5699-5735; param_step of a00_driver.c, gs_iterate's order): the three
+// frequencies, the five exchangeabilities, alpha, each a step of all loci with its evaluation; with the rate moves off the
+// last of them closes the iteration in the same way
 static int gb_scalars(bpa_sampler * s)
 {
   if (s->g_h_ft > 0) { if (!gb_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
+  if (s->g_ft[0] > 0) for (unsigned j = 0; j < 3; ++j)  { if (!gb_step(s, 6, j) || !gb_eval(s, 0)) return 0; }
+  if (s->g_ft[1] > 0) for (unsigned j = 0; j < 6; ++j)  { if (j != 1 && (!gb_step(s, 7, j) || !gb_eval(s, 0))) return 0; }
+  if (s->g_ft[2] > 0)                                   { if (!gb_step(s, 8, 0) || !gb_eval(s, 0)) return 0; }
+  if (gb_subst_moves(s))
+    for (bpa_locus * l : s->loci) l->host_par_stale = true;              // the device blocks moved ahead of the host mirrors
   if (s->g_lr_ft[0] > 0) { if (!gb_step(s, 9) || !gb_eval(s, 0)) return 0; }
   if (s->g_lr_ft[1] > 0 && (s->g_a_mubar > 0 || s->g_b_mubar > 0)) { if (!gb_mubar(s)) return 0; }
   return 1;
@@ -184,7 +227,9 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
   bpa_engine * e = s->eng;
   if (gs_lr_moves(s) && !(s->g_a_mui > 0)) return fail("bpa_sampler: the locus-rate moves need a_mui > 0");
   if (s->g_h_ft > 0 && !(s->g_h_a > 0 && s->g_h_b > 0)) return fail("bpa_sampler: the heredity move needs a, b > 0");
-  if (!gs_lr_ready(s) || !gs_hered_ready(s)) return 0;
+  if (gb_subst_moves(s) && (s->allreduce || s->p2p)) return fail("bpa_sampler: the big-tree sampler's substitution-parameter moves run on one rank");
+  if (s->g_ft[2] > 0 && s->g_rmax > 8) return fail("bpa_sampler: the alpha move takes loci of up to 8 rate categories");
+  if (!gs_lr_ready(s) || !gs_hered_ready(s) || !gb_subst_ready(s)) return 0;
   s->host_current = false;
   const bool prog = gs_prog(s);
   if (s->kernel_bpp && !prog) return fail("bpa_sampler: on the big-tree sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
@@ -238,8 +283,12 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
 static int gb_download(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
+  // (the settle launch of a pending substitution-parameter step is followed by big_par_kernel: the blocks and eigensystems
+  //  are level with the settled values before a plan or bpa_batch_evaluate computes from them)
   if (!gb_step(s, 4) || !gs_prog_pull(s)) return 0;
   HIPCHK(hipMemcpyAsync(s->b_trees.data(), s->b_dev.p, s->nloci*sizeof(gbig::BTree), hipMemcpyDeviceToHost, e->stream));
+  if (s->g_sm.p && !s->g_sm_host.empty())
+    HIPCHK(hipMemcpyAsync(s->g_sm_host.data(), s->g_sm.p, s->g_sm_host.size()*sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (s->g_mui.p)
   {
     HIPCHK(hipMemcpyAsync(s->g_mui_host.data(), s->g_mui.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));

@@ -9,8 +9,11 @@ static int gs_subst_ready(bpa_sampler * s)
 {
   if (!(s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0) || s->g_sm.p) return 1;
   const unsigned T = s->nloci;
-  if (s->g_alljc) return fail("bpa_sampler: the substitution-parameter moves need loci with an eigendecomposition (GTR) and several rate categories");
-  if (s->g_s20) return fail("bpa_sampler: no substitution-parameter moves for amino-acid loci (the empirical models have none; the alpha move is 4-state only here)");
+  // (the big-tree sampler takes loci of any 4-state model side by side: one without an eigendecomposition among them refuses
+  //  the moves; a locus with ONE rate category runs there — its alpha step proposes nothing, a00_driver.c:1187)
+  bool no_eigen = s->g_alljc;
+  if (s->big) { no_eigen = false; for (const bpa_locus * l : s->loci) no_eigen = no_eigen || l->dev.pstride == 2u; }
+  if (no_eigen) return fail("bpa_sampler: the substitution-parameter moves need loci with an eigendecomposition (GTR) and several rate categories");  if (s->g_s20) return fail("bpa_sampler: no substitution-parameter moves for amino-acid loci (the empirical models have none; the alpha move is 4-state only here)");
   if (s->g_sm_host.size() != (size_t)T*11) return fail("bpa_sampler: call bpa_sampler_set_subst_model for every locus before the substitution-parameter moves");
   std::vector<uint32_t> ids(T);
   for (unsigned i = 0; i < T; ++i) ids[i] = s->loci[i]->id;
@@ -1303,7 +1306,7 @@ extern "C" int bpa_sampler_set_subst_model(bpa_sampler_t * s, unsigned i, const 
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
   if (s->comp) { unsigned j; bpa_sampler * p = comp_part(s, i, &j); if (!p) return fail("bpa_sampler_set_subst_model: bad argument"); return bpa_sampler_set_subst_model(p, j, freqs, qrates, alpha); }
   if (i >= s->nloci || !freqs || !qrates || !(alpha > 0)) return fail("bpa_sampler_set_subst_model: bad argument");
-  if (!s->generic) return fail("bpa_sampler_set_subst_model: the loci are JC69 (no substitution parameters to move)");
+  if (!s->generic && !s->big) return fail("bpa_sampler_set_subst_model: the loci are JC69 (no substitution parameters to move)");
   if (s->g_sm_host.size() != (size_t)s->nloci*11) s->g_sm_host.assign((size_t)s->nloci*11, 0.0);
   if (s->uploaded)
     return fail("bpa_sampler_set_subst_model: the sampler is running — set every locus's starting values before bpa_sampler_initialize");

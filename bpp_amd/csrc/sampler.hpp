@@ -1175,6 +1175,7 @@ struct bpa_sampler
   std::vector<gbig::BTree> b_trees;
   DevBuf<gbig::BTree> b_dev, b_undo;
   DevBuf<uint32_t> b_thr;
+  DevBuf<uint8_t> b_par_todo;           // [T] the substitution-parameter moves: the components big_par_kernel owes a locus's parameter block
   // 20-state loci: the generic sampler's steps as the records of the tiled kernels (gsampler.hpp: fmt20)
   bool g_s20 = false;
   unsigned g_ntiles = 0, g_maxops = 0;
@@ -1388,7 +1389,7 @@ extern "C" void bpa_sampler_destroy(bpa_sampler_t * s)
   s->g_len.free(); s->g_lograt.free(); s->g_active.free(); s->g_recs.free(); s->g_mat2.free(); s->g_bmo.free();
   s->g_sm.free(); s->g_sm_old.free(); s->g_ids.free();
   s->g_mui.free(); s->g_mui_old.free(); s->g_lr.free(); s->g_hered.free();
-  s->b_dev.free(); s->b_undo.free(); s->b_thr.free();
+  s->b_dev.free(); s->b_undo.free(); s->b_thr.free(); s->b_par_todo.free();
   s->g_ops20.free(); s->g_oprng.free(); s->g_root20.free(); s->g_mtask.free(); s->g_mpm.free(); s->g_tlocus.free(); s->g_tpat.free(); s->g_ttask.free(); s->g_tn0.free(); s->g_rscaler.free();
   s->v2_wave_off.free(); s->v2_loc.free(); s->v2_pat.free(); s->v2_xbuf.free(); s->v2_grng.free(); s->v2_err.free(); s->v2_prof.free(); s->v2_sched.free(); s->v2_declog.free(); s->v2_sp.free();
   delete s;

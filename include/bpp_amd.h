@@ -436,8 +436,13 @@ int  bpa_sampler_summary(bpa_sampler_t *, double * total_lnl, unsigned long * pr
    frequency but T and each exchangeability but A<->G in turn — a sliding window on its logarithm, the reference
    component taking up the difference — and the gamma shape alpha with a gamma(alpha_a, alpha_b) prior; every proposal
    a full recomputation of the locus with a per-locus decision, all on the device (the category rates of a proposed
-   alpha by pll_compute_gamma_cats there).  Loci with several rate categories and an eigendecomposition only (the
-   generic path); set every locus's starting values first.  Window width 0 = that move is off (default: all off).   */
+   alpha by pll_compute_gamma_cats there).  On the generic sampler (loci with several rate categories and an
+   eigendecomposition) and on the big-tree sampler (step modes 6 / 7 / 8 of big_step_kernel under either move set, the
+   parameter blocks and eigensystems brought level by big_par_kernel; 4-state loci with an eigendecomposition, up to 8
+   categories — a locus with ONE category runs too, its alpha move proposes nothing and draws nothing; one rank); the
+   persistent / sweep kind refuses (its loci are JC69), a composite forwards the widths to its generic parts.  Set every
+   locus's starting values first, before bpa_sampler_initialize.  Window width 0 = that move is off (default: all off);
+   a sampler on which none of the three calls is made computes what it always did, to the bit.   */
 int  bpa_sampler_set_subst_model(bpa_sampler_t *, unsigned i, const double * freqs /* 4 */, const double * qrates /* 6 */, double alpha);
 int  bpa_sampler_get_subst_model(bpa_sampler_t *, unsigned i, double * freqs, double * qrates, double * alpha);
 void bpa_sampler_set_subst_moves(bpa_sampler_t *, double ft_freqs, double ft_qrates, double ft_alpha, double alpha_a, double alpha_b);
