@@ -153,6 +153,9 @@ def lib():
         "bpa_sampler_get_tree": (i, [vp, u, C.POINTER(i), C.POINTER(i), C.POINTER(i), dp, C.POINTER(i),
                                      C.POINTER(i), C.POINTER(i), dp]),
         "bpa_sampler_summary": (i, [vp, dp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
+        "bpa_sampler_set_trace": (i, [vp, u, u]),
+        "bpa_sampler_trace_width": (i, [vp]),
+        "bpa_sampler_trace_read": (C.c_long, [vp, dp, C.c_ulong]),
         "bpa_sampler_enable_timing": (i, [vp, u]),
         "bpa_sampler_set_subst_model": (i, [vp, u, dp, dp, d]),
         "bpa_sampler_get_subst_model": (i, [vp, u, dp, dp, dp]),
@@ -214,7 +217,8 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_device_count", "bpa_engine_cre
             "bpa_sampler_set_program_moves", "bpa_sampler_gibbs_counters",
             "bpa_sampler_set_subst_model", "bpa_sampler_get_subst_model", "bpa_sampler_set_subst_moves",
             "bpa_sampler_set_locus_rates", "bpa_sampler_get_locus_rates", "bpa_sampler_set_locusrate_moves", "bpa_sampler_locusrate_counters",
-            "bpa_sampler_set_heredity", "bpa_sampler_get_heredity", "bpa_sampler_set_heredity_move", "bpa_sampler_heredity_counters"]
+            "bpa_sampler_set_heredity", "bpa_sampler_get_heredity", "bpa_sampler_set_heredity_move", "bpa_sampler_heredity_counters",
+            "bpa_sampler_set_trace", "bpa_sampler_trace_width", "bpa_sampler_trace_read"]
 
 
 def _err():
@@ -709,6 +713,35 @@ class Sampler:
         p, a, l = C.c_ulong(), C.c_ulong(), C.c_ulong()
         _chk(lib().bpa_sampler_summary(self.h, C.byref(tot), C.byref(p), C.byref(a), C.byref(l)))
         return dict(total_lnl=tot.value, proposals=p.value, accepted=a.value, launches=l.value)
+
+    def set_trace(self, every, capacity=4096):
+        """the sample trace: a row [iteration, lnL, taus, thetas] after every `every`-th iteration of iterate(), kept on the
+        device (`capacity` rows there; a full buffer moves to the host, no row is lost); every = 0: off.  burnin() writes none"""
+        _chk(lib().bpa_sampler_set_trace(self.h, int(every), int(capacity)))
+
+    def trace_width(self):
+        return lib().bpa_sampler_trace_width(self.h)
+
+    def trace_read(self, max_rows=None):
+        """the oldest rows (all, or at most max_rows) as an [n, trace_width()] array; they are removed from the trace"""
+        L = lib()
+        n = L.bpa_sampler_trace_read(self.h, None, 0)
+        if n < 0:
+            raise BpaError(_err())
+        n = n if max_rows is None else min(n, int(max_rows))
+        out = np.zeros((n, self.trace_width()))
+        if n:
+            got = L.bpa_sampler_trace_read(self.h, _dp(out), n)
+            if got < 0:
+                raise BpaError(_err())
+            out = out[:got]
+        return out
+
+    def trace(self):
+        """every row recorded since the last call -> dict of arrays: iteration (int64) [n], lnl [n], taus [n, npop], thetas [n, npop]"""
+        r = self.trace_read()
+        npop = (r.shape[1] - 2) // 2
+        return dict(iteration=r[:, 0].astype(np.int64), lnl=r[:, 1].copy(), taus=r[:, 2:2 + npop].copy(), thetas=r[:, 2 + npop:].copy())
 
     def set_subst_model(self, k, freqs, qrates, alpha):
         """starting values of locus k's substitution parameters (the moves of set_subst_moves change them), before initialize;

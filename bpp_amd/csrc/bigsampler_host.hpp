@@ -234,6 +234,11 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
   const bool prog = gs_prog(s);
   if (s->kernel_bpp && !prog) return fail("bpa_sampler: on the big-tree sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
   if (prog && !gs_prog_ready(s)) return 0;
+  // the sample trace: on a row's iteration the step that closes it is settled and the row read from the trees behind it
+  auto rowlog_row = [&]() {
+    return !rowlog_tick(s) || (gb_step(s, 4) &&
+           rowlog_emit(s, reinterpret_cast<const char *>(s->b_dev.p) + offsetof(gbig::BTree, lnl), sizeof(gbig::BTree), nullptr));
+  };
   for (unsigned it = 0; it < iterations; ++it)
   {
     const unsigned ngage = s->maxtips - 1, ngspr = 2*s->maxtips - 2;
@@ -252,7 +257,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
       if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
       HIPCHK(hipEventRecord(ev, e->stream));
       s->gp_pace_n++;
-      if (!gb_scalars(s)) return 0;
+      if (!gb_scalars(s) || !rowlog_row()) return 0;
       continue;
     }
     if (s->sp.theta_alpha > 0)
@@ -275,7 +280,7 @@ static int gb_iterate(bpa_sampler * s, unsigned iterations)
     const double lnc = s->sp.ft_mix*(a00_rndu(&s->grng) - 0.5), c = std::exp(lnc);
     const double uacc = a00_rndu(&s->grng);
     if (!gb_step(s, 3, 0, 0.0, c, lnc) || !gb_eval(s, 1) || !gb_decide(s, uacc, -1, 0.0, c, lnc)) return 0;
-    if (!gb_scalars(s)) return 0;
+    if (!gb_scalars(s) || !rowlog_row()) return 0;
   }
   return 1;
 }

@@ -316,6 +316,33 @@ static int comp_summary(bpa_sampler * s, double * total_lnl, unsigned long * pro
   if (launches) *launches = la;
   return 1;
 }
+// the sample trace of loci of several kinds (bpa_sampler_trace_read): every part traced its own loci through the same
+// iterations; the iteration, tau and theta are part 0's (every part holds the same), lnL the parts' lnL of the same row added
+// in part order
+static long comp_trace_read(bpa_sampler * s, double * rows, unsigned long max_rows)
+{
+  unsigned long avail = 0;
+  bool first = true;
+  for (auto * p : s->comp->parts)
+  {
+    unsigned long a = 0;
+    if (!rowlog_collect(p, &a)) return -1;
+    avail = first ? a : std::min(avail, a); first = false;
+  }
+  if (!rows) return (long)avail;
+  const unsigned long n = std::min(avail, max_rows);
+  const size_t w = rowlog_width(s);
+  std::vector<double> tmp((size_t)n*w);
+  first = true;
+  for (auto * p : s->comp->parts)
+  {
+    if (n && p->rowlog_w != w) { fail("bpa_sampler_trace_read: the parts' rows differ in width"); return -1; }
+    rowlog_take(p, first ? rows : tmp.data(), n);
+    if (!first) for (unsigned long r = 0; r < n; ++r) rows[r*w + 1] += tmp[r*w + 1];
+    first = false;
+  }
+  return (long)n;
+}
 static int comp_timing(bpa_sampler * s, double * sweep_ms, unsigned long * sweep_launches, double * allloci_ms, unsigned long * allloci_launches)
 {
   double a = 0, c = 0; unsigned long b = 0, d = 0;

@@ -1260,6 +1260,10 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
     // ... then the loci's rates and their mean (method.c:5745-5773; mui_step / mubar_step of a00_driver.c)
     if (s->g_lr_ft[0] > 0) { if (!gs_step(s, 9) || !gs_eval(s, 0)) return 0; }
     if (s->g_lr_ft[1] > 0 && (s->g_a_mubar > 0 || s->g_b_mubar > 0)) { if (!gs_mubar(s)) return 0; }
+    // the sample trace: on a row's iteration the last step is settled (the launch joins the part-batches' streams first) and
+    // the row read from the trees behind it — no levelling of the roots' buffers, nothing copied to the host
+    if (rowlog_tick(s) && (!gs_step(s, 4) ||
+        !rowlog_emit(s, reinterpret_cast<const char *>(s->g_dev.p) + offsetof(gsm::GTree, lnl), sizeof(gsm::GTree), nullptr))) return 0;
   }
   return gs_join(s);                 // whoever uses the engine's stream next sees both halves
 }

@@ -1173,6 +1173,39 @@ __global__ void __launch_bounds__(1024) lnl_sum_kernel(const double * __restrict
   if (threadIdx.x == 0) out[0] = sh[0];
 }
 
+// One row of a sampler's sample trace (bpa_sampler_set_trace): [iteration, lnL, tau[0 .. npop), theta[0 .. npop)], written
+// after the iteration's state has settled, by one workgroup of 1 024 threads on the sampler's stream.  lnL is the sum of the
+// loci's own lnl — the double at lnl_base + i*stride bytes: a field of smp::Tree, gsm::GTree or gbig::BTree — in
+// lnl_sum_kernel's order: thread t adds loci t, t + 1024, ... in turn, then the LDS tree sh[t] += sh[t + w], w = 512 ... 1.
+// No atomics: two runs from one seed write the same bits.  The row goes to slot (*nrows - base) of `rows` (base: the rows the
+// host has already taken away), with plain vector stores; thread 0 then advances *nrows, which the next launch on the stream
+// sees.  A slot beyond `capacity` is never written.  err (the persistent kernel's error word, or null): while it is set the
+// launch before this one gave up and left the loci as it found them — no row, the counter stays; the iterations run again.
+__global__ void __launch_bounds__(1024) trace_row_kernel(const char * __restrict__ lnl_base, size_t stride, uint32_t n,
+                                                         const double * __restrict__ taus, const double * __restrict__ thetas,
+                                                         uint32_t npop, double iteration, double * __restrict__ rows,
+                                                         uint32_t capacity, unsigned long long * nrows,
+                                                         unsigned long long base, const int * __restrict__ err)
+{
+  __shared__ double sh[1024];
+  if (err && *err) return;
+  const unsigned long long slot = *nrows - base;       // (every thread reads it before the last barrier, thread 0 writes it after)
+  if (slot >= capacity) return;
+  double acc = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += 1024) acc += *reinterpret_cast<const double *>(lnl_base + (size_t)i*stride);
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t w = 512; w > 0; w >>= 1)
+  {
+    if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  const uint32_t t = threadIdx.x, width = 2u + 2u*npop;
+  if (t < width)
+    rows[slot*width + t] = t == 0 ? iteration : t == 1 ? sh[0] : t < 2u + npop ? taus[t - 2u] : thetas[t - 2u - npop];
+  if (t == 0) *nrows = slot + base + 1ull;
+}
+
 // ================================================================== K4 / K5 ==
 // P(t) for one (branch, rate category).  4-state: one lane does the 16 entries.
 __device__ __forceinline__ void pmatrix_identity(double * p, int S)

@@ -1241,12 +1241,30 @@ struct bpa_sampler
   DevBuf<smp::Species> v2_sp;
   smp::Species v2_sp_sent{};            // what v2_sp holds
   // the persistent launches since the last download, oldest first: what a launch that gave up (a shared device) is run again from
-  struct V2Launch { a00_rng_t grng_before; unsigned chunk; bool mix_pending, logpr_stale; };
+  struct V2Launch { a00_rng_t grng_before; unsigned chunk; bool mix_pending, logpr_stale; unsigned long long rowlog_it_before; };
   std::vector<V2Launch> v2_log;
   bool kernel_bpp = false, v2_grng_sent = false;   // BPP's own generator + Bactrian-Laplace windows (bpa_sampler_set_proposal_kernel); the global stream then lives on the device
   bpa_p2p * p2p = nullptr;              // several GPUs, the sums exchanged INSIDE the persistent kernel over xGMI mailboxes (bpa_sampler_set_p2p)
   unsigned long v2_iters = 0;           // iterations run by persistent launches (bpa_sampler_timing)
+  // ---- the sample trace (bpa_sampler_set_trace: rows of tau, theta and lnL every rowlog_every iterations; nothing to do with the
+  // BPA_SMP_TRACE diagnostic, env_trace).  rowlog_it: iterations of bpa_sampler_iterate counted since set_trace (not while
+  // rowlog_hold: burn-in); the device holds rowlog_rows [rowlog_cap][width] and the count of all rows ever written, rowlog_n;
+  // rowlog_base of them have been moved to rowlog_store (the host-side store, oldest first from rowlog_head on); rowlog_enq:
+  // row launches since the device buffer was last emptied (an upper bound of the rows in it)
+  unsigned rowlog_every = 0, rowlog_cap = 0, rowlog_enq = 0, rowlog_w = 0;      // (rowlog_w: the doubles of a row the buffers were made for)
+  bool rowlog_hold = false;
+  unsigned long long rowlog_it = 0, rowlog_base = 0;
+  DevBuf<double> rowlog_rows;
+  DevBuf<unsigned long long> rowlog_n;
+  std::vector<double> rowlog_store; size_t rowlog_head = 0;
 };
+
+static bool rowlog_on(const bpa_sampler * s) { return s->rowlog_every && !s->rowlog_hold; }
+static unsigned rowlog_width(const bpa_sampler * s) { return 2u + 2u*(unsigned)s->sp.npop; }
+static int rowlog_flush(bpa_sampler * s);
+static int rowlog_emit(bpa_sampler * s, const void * lnl0, size_t stride, const int * err);
+// the iterations up to the next row (the persistent launches end there)
+static unsigned rowlog_until_row(const bpa_sampler * s) { return s->rowlog_every - (unsigned)(s->rowlog_it % s->rowlog_every); }
 
 static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, bool * plain);
 static void comp_destroy(bpa_sampler * s);
@@ -1259,6 +1277,7 @@ static int comp_timing(bpa_sampler * s, double * sweep_ms, unsigned long * sweep
 static int comp_work(bpa_sampler * s, double * bytes, unsigned long * node_updates, unsigned long * pattern_updates, unsigned long * sweeps);
 static bpa_sampler * comp_part(bpa_sampler * s, unsigned i, unsigned * j);
 static bpa_sampler * comp_part0(bpa_sampler * s);
+static long comp_trace_read(bpa_sampler * s, double * rows, unsigned long max_rows);
 template <class F> static int comp_each(bpa_sampler * s, F f);
 #define COMP_FAIL(msg) do { if (s->comp) return fail(msg); } while (0)
 
@@ -1392,6 +1411,7 @@ extern "C" void bpa_sampler_destroy(bpa_sampler_t * s)
   s->b_dev.free(); s->b_undo.free(); s->b_thr.free(); s->b_par_todo.free();
   s->g_ops20.free(); s->g_oprng.free(); s->g_root20.free(); s->g_mtask.free(); s->g_mpm.free(); s->g_tlocus.free(); s->g_tpat.free(); s->g_ttask.free(); s->g_tn0.free(); s->g_rscaler.free();
   s->v2_wave_off.free(); s->v2_loc.free(); s->v2_pat.free(); s->v2_xbuf.free(); s->v2_grng.free(); s->v2_err.free(); s->v2_prof.free(); s->v2_sched.free(); s->v2_declog.free(); s->v2_sp.free();
+  s->rowlog_rows.free(); s->rowlog_n.free();
   delete s;
 }
 
@@ -2124,7 +2144,32 @@ extern "C" unsigned bpa_burnin_schedule(unsigned burnin, unsigned * after, unsig
   return n + 1;
 }
 
+static int sampler_burnin_run(bpa_sampler_t * s, unsigned iterations, double * finetune);
+// The sample trace does not see the burn-in (the program records nothing there either): its count is held and no row is written.
+// A persistent launch that gave up is run again with the trace as it is when the re-run happens, so a traced sampler settles
+// what is in flight where the burn-in starts and where it ends.
+static int rowlog_settle(bpa_sampler * s)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (s->comp || !s->uploaded || s->v2_log.empty()) return 1;
+  return set_device(s->eng) && sampler_download(s);
+}
+static void rowlog_set_hold(bpa_sampler * s, bool hold)
+{
+  s->rowlog_hold = hold;
+  if (s->comp) (void)comp_each(s, [&](bpa_sampler * p) { p->rowlog_hold = hold; return 1; });
+}
 extern "C" int bpa_sampler_burnin(bpa_sampler_t * s, unsigned iterations, double * finetune)
+{
+  if (!s->rowlog_every) return sampler_burnin_run(s, iterations, finetune);
+  if (!rowlog_settle(s)) return 0;
+  rowlog_set_hold(s, true);
+  const int ok = sampler_burnin_run(s, iterations, finetune) && rowlog_settle(s);
+  rowlog_set_hold(s, false);
+  return ok;
+}
+
+static int sampler_burnin_run(bpa_sampler_t * s, unsigned iterations, double * finetune)
 {
   // what the rule needs is checked BEFORE the chain moves (a sampler that cannot adapt must not be left half-way through)
   if (iterations >= 200)
@@ -2253,6 +2298,130 @@ extern "C" int bpa_sampler_set_allreduce(bpa_sampler_t * s, bpa_allreduce_fn fn,
   return 1;
 }
 
+// ---- the sample trace (bpa_sampler_set_trace): a row is ONE launch of trace_row_kernel behind the launches that settled the
+// iteration's state, on the same stream; the host waits only when the device buffer is full (rowlog_flush: once per rowlog_cap
+// rows) and in bpa_sampler_trace_read
+// move the device buffer's rows to the host-side store (waits for the stream)
+static int rowlog_flush(bpa_sampler * s)
+{
+  bpa_engine * e = s->eng;
+  if (!s->rowlog_rows.p) return 1;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  unsigned long long n = 0;
+  HIPCHK(hipMemcpy(&n, s->rowlog_n.p, sizeof n, hipMemcpyDeviceToHost));
+  const unsigned long long have = n - s->rowlog_base;
+  if (have > s->rowlog_cap) return fail("bpa_sampler: the sample trace's row counter is beyond its buffer");
+  if (have)
+  {
+    if (s->rowlog_head) { s->rowlog_store.erase(s->rowlog_store.begin(), s->rowlog_store.begin() + (std::ptrdiff_t)s->rowlog_head); s->rowlog_head = 0; }
+    const size_t old = s->rowlog_store.size(), add = (size_t)have*s->rowlog_w;
+    s->rowlog_store.resize(old + add);
+    HIPCHK(hipMemcpy(s->rowlog_store.data() + old, s->rowlog_rows.p, add*sizeof(double), hipMemcpyDeviceToHost));
+  }
+  s->rowlog_base = n; s->rowlog_enq = 0;           // (the kernel's slot is its count minus rowlog_base: nothing to reset on the device)
+  return 1;
+}
+
+// enqueue the row of iteration rowlog_it: the loci's lnl are the doubles at lnl0 + i*stride of the settled trees; err: the
+// persistent kernel's error word (a launch that gave up: no row) or null
+static int rowlog_emit(bpa_sampler * s, const void * lnl0, size_t stride, const int * err)
+{
+  bpa_engine * e = s->eng;
+  const unsigned w = rowlog_width(s);
+  if (!s->rowlog_rows.p)
+  {
+    const unsigned long long zero = 0;
+    if (!s->rowlog_rows.reserve((size_t)s->rowlog_cap*w) || !s->rowlog_n.reserve(1)) return fail("bpa_sampler: out of device memory (sample trace)");
+    HIPCHK(hipMemcpy(s->rowlog_n.p, &zero, sizeof zero, hipMemcpyHostToDevice));
+    s->rowlog_w = w; s->rowlog_base = 0; s->rowlog_enq = 0;
+  }
+  if (w != s->rowlog_w) return fail("bpa_sampler: the species tree changed size under a sample trace (call bpa_sampler_set_trace again)");
+  if (s->rowlog_enq >= s->rowlog_cap && !rowlog_flush(s)) return 0;
+  hipLaunchKernelGGL(trace_row_kernel, dim3(1), dim3(1024), 0, e->stream, static_cast<const char *>(lnl0), stride, e->usedata ? (uint32_t)s->nloci : 0u,
+                     (const double *)s->taus.p, (const double *)(s->taus.p + smp::MAXPOP), (uint32_t)s->sp.npop, (double)s->rowlog_it,
+                     s->rowlog_rows.p, (uint32_t)s->rowlog_cap, s->rowlog_n.p, s->rowlog_base, err);
+  HIPCHK(hipGetLastError());
+  s->rowlog_enq++; s->launches++;
+  return 1;
+}
+
+// the end of an iteration on the paths that launch per step: counts it, true when its row is due
+static bool rowlog_tick(bpa_sampler * s) { return rowlog_on(s) && ++s->rowlog_it % s->rowlog_every == 0; }
+
+static void rowlog_drop(bpa_sampler * s)
+{
+  s->rowlog_rows.free(); s->rowlog_n.free();
+  s->rowlog_store.clear(); s->rowlog_store.shrink_to_fit(); s->rowlog_head = 0;
+  s->rowlog_it = 0; s->rowlog_base = 0; s->rowlog_enq = 0; s->rowlog_w = 0;
+}
+
+extern "C" int bpa_sampler_set_trace(bpa_sampler_t * s, unsigned every, unsigned capacity)
+{
+  bpa_engine * e = s->eng;
+  std::lock_guard<std::recursive_mutex> lock_(e->mtx);
+  if (every && !capacity) return fail("bpa_sampler_set_trace: a trace needs room for at least one row (capacity > 0)");
+  if (s->comp)
+  {
+    if (!comp_each(s, [&](bpa_sampler * p) { return bpa_sampler_set_trace(p, every, capacity); })) return 0;
+    s->rowlog_every = every; s->rowlog_cap = every ? capacity : 0u;
+    return 1;
+  }
+  if (!set_device(e)) return 0;
+  // (persistent launches in flight belong to the trace as it was: a launch that gave up is run again under the old count)
+  if (s->uploaded && !s->v2_log.empty() && !sampler_download(s)) return 0;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  rowlog_drop(s);
+  s->rowlog_every = every; s->rowlog_cap = every ? capacity : 0u;
+  return 1;
+}
+
+extern "C" int bpa_sampler_trace_width(bpa_sampler_t * s)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  return (int)rowlog_width(s);
+}
+
+// every row written so far is in the store afterwards; *avail: their number
+static int rowlog_collect(bpa_sampler * s, unsigned long * avail)
+{
+  bpa_engine * e = s->eng;
+  *avail = 0;
+  if (!s->rowlog_every) return 1;
+  if (!set_device(e)) return 0;
+  if (s->uploaded && s->v2_ok && !s->v2_log.empty())
+  {
+    // a persistent launch that gave up wrote no row, nor did the launches behind it: their iterations run again first
+    int err = 0;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(&err, s->v2_err.p, sizeof err, hipMemcpyDeviceToHost));
+    if (err && !sampler_download(s)) return 0;
+  }
+  if (!rowlog_flush(s)) return 0;
+  *avail = s->rowlog_w ? (unsigned long)((s->rowlog_store.size() - s->rowlog_head)/s->rowlog_w) : 0ul;
+  return 1;
+}
+
+static long rowlog_take(bpa_sampler * s, double * rows, unsigned long n)
+{
+  const size_t cnt = (size_t)n*s->rowlog_w;
+  if (cnt) std::memcpy(rows, s->rowlog_store.data() + s->rowlog_head, cnt*sizeof(double));
+  s->rowlog_head += cnt;
+  if (s->rowlog_head == s->rowlog_store.size()) { s->rowlog_store.clear(); s->rowlog_head = 0; }
+  return (long)n;
+}
+
+extern "C" long bpa_sampler_trace_read(bpa_sampler_t * s, double * rows, unsigned long max_rows)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  unsigned long avail = 0;
+  if (!s->comp)
+  {
+    if (!rowlog_collect(s, &avail)) return -1;
+    return rows ? rowlog_take(s, rows, std::min(avail, max_rows)) : (long)avail;
+  }
+  return comp_trace_read(s, rows, max_rows);
+}
+
 // the whole iteration(s) as persistent launches: GAGE + GSPR of every locus, THETA, TAU per divergence, MIX — state in
 // LDS from the first proposal to the last decision (sweep2.hpp)
 // in_kernel_allloci = false (several ranks): only the per-locus sweep of ONE iteration; the all-loci steps then run as
@@ -2281,11 +2450,13 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
   const unsigned bs = s->v2_nt == 4 ? smp2::Cfg<4>::BS : smp2::Cfg<8>::BS;
   while (iterations)
   {
-    const unsigned chunk = std::min(iterations, 4096u);          // (bounds one launch's duration)
+    unsigned chunk = std::min(iterations, 4096u);                // (bounds one launch's duration)
     smp2::Args a{};
     a.wave_off = s->v2_wave_off.p; a.loc = s->v2_loc.p; a.pat = s->v2_pat.p; a.trees = s->trees.p; a.taus = s->taus.p;
     if (s->v2_log.size() >= 65536u && !sampler_download(s)) return 0;            // (bounds the log of a caller that never looks)
-    s->v2_log.push_back({s->grng, chunk, s->mix_pending, s->logpr_stale});
+    const bool rowlog = allloci && rowlog_on(s);                 // the sample trace: a launch also ends where a row is due
+    if (rowlog) chunk = std::min(chunk, rowlog_until_row(s));
+    s->v2_log.push_back({s->grng, chunk, s->mix_pending, s->logpr_stale, s->rowlog_it});
     // what the one-launch-per-step path left pending is settled while this launch loads (Args::snap ...)
     a.snap = s->snap.p; a.mix_flag = s->flag.p; a.epoch = s->mix_pending ? s->epoch : 0u; a.refresh_logpr = s->logpr_stale ? 1u : 0u;
     s->mix_pending = false; s->logpr_stale = false;
@@ -2340,6 +2511,14 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
     if (!s->kernel_bpp) for (unsigned long k = 0; k < (unsigned long)chunk*draws_per_iter; ++k) (void)a00_rndu(&s->grng);
     s->launches++; s->sweeps += chunk; s->v2_iters += chunk;
     iterations -= chunk;
+    if (rowlog)
+    {
+      // the launch left the settled state in s->trees / s->taus: the row is read from there, behind it on the stream (a launch
+      // that gave up left the error word set: trace_row_kernel then writes nothing, and sampler_download's rewind puts the count back)
+      s->rowlog_it += chunk;
+      if (s->rowlog_it % s->rowlog_every == 0 &&
+          !rowlog_emit(s, reinterpret_cast<const char *>(s->trees.p) + offsetof(smp::Tree, lnl), sizeof(smp::Tree), s->v2_err.p)) return 0;
+    }
   }
   return 1;
 }
@@ -2430,6 +2609,9 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
     const double uacc = a00_rndu(&s->grng);
     if (!sampler_launch(s, 1, c, lnc)) return 0;                 // mixing proposal of every locus
     if (!sampler_decide(s, uacc, -1, -1, 0.0, c, lnc)) return 0;
+    // the sample trace: the MIX decision is pending in the flag, so the row is read behind the settle launch a download would issue
+    if (rowlog_tick(s) && (!sampler_launch(s, 2, 1.0) ||
+        !rowlog_emit(s, reinterpret_cast<const char *>(s->trees.p) + offsetof(smp::Tree, lnl), sizeof(smp::Tree), nullptr))) return 0;
   }
   return 1;
 }
@@ -2512,6 +2694,7 @@ static int sampler_download(bpa_sampler * s)
           s->launches--; s->sweeps -= l.chunk; s->v2_iters -= l.chunk;
           if (!s->kernel_bpp) s->grng = l.grng_before;
           s->mix_pending = l.mix_pending; s->logpr_stale = l.logpr_stale;
+          s->rowlog_it = l.rowlog_it_before;            // (the sample trace: those launches' rows were not written; the re-run writes them, in order)
         }
         if (left != 0) return fail("bpa_sampler: the persistent kernel reports iterations it did not run that no launch of the log accounts for");
       }

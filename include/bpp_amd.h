@@ -431,6 +431,39 @@ int  bpa_sampler_get_tree(bpa_sampler_t *, unsigned i, int * left, int * right, 
 int  bpa_sampler_get_tree_msc(bpa_sampler_t *, unsigned i, int * pop, double * logpr);
 int  bpa_sampler_summary(bpa_sampler_t *, double * total_lnl, unsigned long * proposals,
                          unsigned long * accepted, unsigned long * launches);
+/* The sample trace: what BPP writes to mcmc.txt every `sampfreq` iterations (taus, thetas, lnL), recorded on the device while
+   the chain runs — no download, no copy of the trees, no wait for the stream per sample.  (Not the BPA_SMP_TRACE diagnostic.)
+     bpa_sampler_set_trace    every = 0: off, buffers freed, unread rows dropped.  Otherwise a row is recorded after iterations
+                              every, 2 every, ... of bpa_sampler_iterate, counted from this call; the count carries over from
+                              one bpa_sampler_iterate to the next and does not advance inside bpa_sampler_burnin (which writes
+                              no rows; with a trace on it settles the launches in flight where it starts and ends) or
+                              bpa_sampler_adapt_finetune.  capacity: the rows the device buffer holds; every > 0 with
+                              capacity = 0 is refused.  Calling it again starts a new trace (count 0, unread rows dropped).
+     bpa_sampler_trace_width  doubles per row: 2 + 2 npop, npop = 2*species - 1.
+     bpa_sampler_trace_read   copies out the oldest rows, at most max_rows, removes them and returns their number (-1: error);
+                              rows = NULL: the number available.  The only call that waits for the device on the trace's
+                              behalf — apart from one wait per `capacity` rows: before the row that would overflow the device
+                              buffer is enqueued, its rows move to a host-side store, so no row is lost and
+                              bpa_sampler_iterate never fails for want of room; the store is served first.
+   Row: [iteration, lnL, tau[0 .. npop), theta[0 .. npop)], all doubles, in the order of bpa_sampler_get_taus /
+   bpa_sampler_get_thetas; iteration = the trace's count.  It holds what a caller would have read by stopping there —
+   bpa_sampler_iterate up to that iteration, then bpa_sampler_get_taus, bpa_sampler_get_thetas and every locus's
+   bpa_sampler_get_tree(...).lnl: tau and theta are the same bits; lnL is the sum of those per-locus values over the sampler's
+   own loci in a fixed order (one workgroup of 1 024 threads, csrc/kernels.hpp trace_row_kernel, the order of lnl_sum_kernel):
+   thread t adds loci t, t + 1024, t + 2048, ... in turn, starting from 0.0; then the tree sh[t] += sh[t + w] for t < w,
+   w = 512, 256, ... 1; lnL = sh[0].  No atomics: two runs from one seed give identical rows.  With usedata = 0
+   (bpa_engine_set_options) lnL is 0.0.  Tracing changes nothing else: a traced and an untraced run from one seed end in the
+   same state, bit for bit.
+   How: the persistent kernel's launches also end where a row is due, and one launch of trace_row_kernel follows on the same
+   stream (a launch that gave up — see bpa_sampler_iterate — writes no row; its iterations and their rows are run again, in
+   order, by bpa_sampler_trace_read or whatever else reads the sampler's state); the paths with one launch per step, the
+   generic and the big-tree sampler settle the step that closes the iteration on a row's iteration only, then launch the row
+   kernel.  A composite traces every part's own loci; its rows are merged on the host: iteration, tau and theta from part 0,
+   lnL the parts' lnL of the same row added in part order.  Several ranks: nothing is exchanged — each rank's rows carry the
+   lnL of its own shard of the loci and the taus and thetas every rank holds identically; the caller adds the shards' lnL. */
+int  bpa_sampler_set_trace(bpa_sampler_t *, unsigned every, unsigned capacity);
+int  bpa_sampler_trace_width(bpa_sampler_t *);                 /* doubles per row: 2 + 2*(2*species-1) */
+long bpa_sampler_trace_read(bpa_sampler_t *, double * rows, unsigned long max_rows);
 /* The per-locus substitution-parameter moves of a GTR + Gamma analysis (propose_freqs locus.c:2782, propose_qrates
    locus.c:3168, propose_alpha prop_gamma.c:52; after the mixing step as in cmd_run, method.c:5699-5735): each base
    frequency but T and each exchangeability but A<->G in turn — a sliding window on its logarithm, the reference
