@@ -144,6 +144,7 @@ def lib():
         "bpa_exchange_layout": (i, [u, u, u, u, C.POINTER(u)]),
         "bpa_sampler_set_tau_prior": (None, [vp, d, d]),
         "bpa_sampler_set_theta_prior": (None, [vp, d, d, d]),
+        "bpa_sampler_set_prior_kinds": (i, [vp, i, i]),
         "bpa_sampler_get_thetas": (i, [vp, dp]),
         "bpa_sampler_set_allreduce": (i, [vp, vp, vp, vp, u]),
         "bpa_sampler_get_taus": (i, [vp, dp]),
@@ -211,7 +212,7 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_device_count", "bpa_engine_cre
             "bpa_sampler_set_species_tree", "bpa_sampler_set_tip_species", "bpa_sampler_set_finetune",
             "bpa_finetune_onestep", "bpa_sampler_adapt_finetune", "bpa_sampler_burnin", "bpa_burnin_schedule", "bpa_sweep_schedule", "bpa_exchange_layout",
             "bpa_sampler_set_tau_prior", "bpa_sampler_get_taus", "bpa_sampler_get_tree_msc",
-            "bpa_sampler_set_theta_prior", "bpa_sampler_get_thetas", "bpa_sampler_set_allreduce",
+            "bpa_sampler_set_theta_prior", "bpa_sampler_set_prior_kinds", "bpa_sampler_get_thetas", "bpa_sampler_set_allreduce",
             "bpa_sampler_iterate", "bpa_sampler_get_tree", "bpa_sampler_summary",
             "bpa_sampler_enable_timing", "bpa_sampler_timing", "bpa_sampler_work", "bpa_sampler_kind", "bpa_sampler_streams", "bpa_sampler_set_p2p", "bpa_sampler_set_proposal_kernel",
             "bpa_sampler_set_program_moves", "bpa_sampler_gibbs_counters",
@@ -657,6 +658,22 @@ class Sampler:
 
     def set_theta_prior(self, alpha, beta, finetune):
         lib().bpa_sampler_set_theta_prior(self.h, alpha, beta, finetune)
+
+    PRIOR_KINDS = {"gamma": 0, "invgamma": 1}
+
+    def set_prior_kinds(self, theta="gamma", tau="gamma"):
+        """The families (alpha, beta) of set_theta_prior / set_tau_prior belong to: "gamma" (BPP's 'thetaprior = gamma a b',
+        the default here) or "invgamma" (BPP's own default: 'thetaprior = invgamma a b e', 'tauprior = invgamma a b'); the
+        integers 0 / 1 are taken too.  Before initialize.  On the generic sampler (BPA_SMP_GENERIC=1 forces it), the big-tree
+        sampler and the one-launch-per-step sampler (BPA_SMP_V1=1), under both move sets; the persistent kernel, a composite
+        and a sampler that exchanges sums with other ranks have the gamma priors only and raise"""
+        def kind(k):
+            if isinstance(k, str):
+                if k not in self.PRIOR_KINDS:
+                    raise BpaError(f"set_prior_kinds: 'gamma' or 'invgamma', not {k!r}")
+                return self.PRIOR_KINDS[k]
+            return int(k)
+        _chk(lib().bpa_sampler_set_prior_kinds(self.h, kind(theta), kind(tau)))
 
     def set_allreduce(self, fn, device_sum_ptr, first_locus):
         """fn(device_ptr:int, count:int, stream:int) -> truthy; enqueues the sum all-reduce of `count` device doubles

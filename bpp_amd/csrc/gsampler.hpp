@@ -823,7 +823,9 @@ __global__ void __launch_bounds__(1024) gdec_theta_sums_kernel(const int8_t * __
 
 // PHASE 0: THETA (v: 4 doubles per population) + the first TAU's window; 1: TAU q (v: 8 doubles) + the next step's proposal
 // (next < npop: TAU `next`, next == npop: MIX with its re-draws); 2: MIX (v: 1 double).  One wave; dynamic LDS = smp2::WgBase.
-template <int PHASE>
+// TK: the theta prior's family (smp::theta_kind: 0 gamma, 1 inverse gamma), compiled into the control-wave functions; the root
+// tau's family is one uniform branch on sp (a00_tau_prior_lnratio / a00_mix_tau_prior_lnratio).
+template <int PHASE, int TK>
 __global__ void __launch_bounds__(64) gdec_kernel(GDecState * __restrict__ st, const double * __restrict__ v, const Species sp, const uint32_t tm,
                                                   const int q, const int next, const uint32_t epoch, uint32_t * __restrict__ flag,
                                                   uint32_t * __restrict__ counters, double * __restrict__ taus)
@@ -870,7 +872,7 @@ __global__ void __launch_bounds__(64) gdec_kernel(GDecState * __restrict__ st, c
       wg.xtot[(2*kx + 1) & 31] = bad ? qnan : (double)gdec_join64(v[4*lane + 1], v[4*lane + 2])*(1.0/1099511627776.0);
     }
     smp2::wsync();
-    g.r = smp2::prog_theta_decide((uint32_t)g.r, tm, slidem, tslide, 1, -1, 0);
+    g.r = smp2::prog_theta_decide<TK>((uint32_t)g.r, tm, slidem, tslide, 1, -1, 0);
     const uint32_t accm = wg.dec.accm;
     c_prop = (uint32_t)__popc(tm); c_acc = (uint32_t)__popc(accm);
     c_gprop = (uint32_t)__popc(tm & ~slidem); c_gacc = (uint32_t)__popc(accm & tm & ~slidem);
@@ -884,12 +886,12 @@ __global__ void __launch_bounds__(64) gdec_kernel(GDecState * __restrict__ st, c
     const double tq_old = wg.tau[q], tq_lo = fmax(wg.tau[cl], wg.tau[cr]), tq_hi = pq >= 0 ? wg.tau[pq] : 999.0;
     const double tq_new = reflect(tq_old + sp.ft_tau*tau_w, tq_lo, tq_hi);
     double lnprior = 0;
-    if (pq < 0 && sp.tau_alpha > 0) lnprior = (sp.tau_alpha - 1 - (nsp - 1) + 1)*log(tq_new/tq_old) - sp.tau_beta*(tq_new - tq_old);
+    if (pq < 0 && sp.tau_alpha > 0) lnprior = a00_tau_prior_lnratio(smp::tau_kind(sp), sp.tau_alpha, sp.tau_beta, nsp, tq_old, tq_new);
     const bool bad = v[7] != 0.0;
     if (lane == 0) { wg.xtot[0] = v[0]; wg.xtot[1] = 0.0; }
     if (lane >= 2u && lane <= 4u) wg.xtot[lane] = bad ? qnan : (double)gdec_join64(v[2*lane - 3], v[2*lane - 2])*(1.0/1099511627776.0);
     smp2::wsync();
-    g.r = smp2::prog_tau_decide((uint32_t)g.r, tm, q, 0, lnprior, false);
+    g.r = smp2::prog_tau_decide<TK>((uint32_t)g.r, tm, q, 0, lnprior, false);
     const bool accept = wg.dec.acc_step != 0u;
     const uint32_t rd_mask = wg.dec.rd_mask;
     c_prop = 1; c_acc = accept ? 1u : 0u; pj4 = 1; pj5 = accept ? 1ull : 0ull;
@@ -912,7 +914,7 @@ __global__ void __launch_bounds__(64) gdec_kernel(GDecState * __restrict__ st, c
     else
     {
       mix_lnc = sp.ft_mix*wprop; mix_c = exp(mix_lnc);
-      g.r = smp2::prog_mix_redraw((uint32_t)g.r, tm, mix_c);
+      g.r = smp2::prog_mix_redraw<TK>((uint32_t)g.r, tm, mix_c);
     }
   }
   else
@@ -921,7 +923,7 @@ __global__ void __launch_bounds__(64) gdec_kernel(GDecState * __restrict__ st, c
     if (sp.tau_alpha > 0)
     {
       const double troot = wg.tau[npop - 1];
-      lnacc += (sp.tau_alpha - 1)*mix_lnc - sp.tau_beta*(troot*mix_c - troot) - (double)(nsp - 2)*mix_lnc;
+      lnacc += a00_mix_tau_prior_lnratio(smp::tau_kind(sp), sp.tau_alpha, sp.tau_beta, nsp, mix_lnc, troot, troot*mix_c);
     }
     lnacc += wg.dec.lnacc_theta;
     const uint32_t rd_mask = wg.dec.rd_mask;

@@ -870,6 +870,7 @@ static int gs_prog_theta(bpa_sampler * s)
   const int npop = s->sp.npop;
   unsigned int gz = (unsigned int)s->grng;
   int slide[smp::MAXPOP]; double tnew[smp::MAXPOP], fa[smp::MAXPOP], fb[smp::MAXPOP];
+  const int tk = smp::theta_kind(s->sp);
   uint32_t onmask = 0;
   for (int p = 0; p < npop; ++p)
   {
@@ -905,7 +906,7 @@ static int gs_prog_theta(bpa_sampler * s)
   {
     fa[p] = fb[p] = NAN;
     if (!s->has_theta[p] || bad || slide[p]) continue;
-    a00_theta_conditional_invgamma(s->sp.theta_alpha, s->sp.theta_beta, (long)s->gp_k[p], s->gp_T[p], &fa[p], &fb[p]);
+    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, (long)s->gp_k[p], s->gp_T[p], &fa[p], &fb[p]);
     if (fa[p] == fa[p]) tnew[p] = 1/(a00_bpp_rndgamma(&gz, fa[p])/fb[p]);
   }
   gsm::GApply a{};
@@ -918,7 +919,8 @@ static int gs_prog_theta(bpa_sampler * s)
     const double T = s->gp_T[p];
     if (!bad)
     {
-      if (slide[p]) lnacc = a00_theta_lnacc((long)s->gp_k[p], T, s->gp_theta[p], tnew[p], s->sp.theta_alpha, s->sp.theta_beta);
+      if (slide[p]) lnacc = a00_theta_lnacc_kind(tk, (long)s->gp_k[p], T, s->gp_theta[p], tnew[p], s->sp.theta_alpha, s->sp.theta_beta);
+      else if (fa[p] == fa[p] && tk == A00_PRIOR_INVGAMMA) lnacc = tnew[p] == tnew[p] ? 0.0 : NAN;      // (the conditional itself: accepted, nothing drawn)
       else if (fa[p] == fa[p])
         lnacc = a00_theta_lnacc((long)s->gp_k[p], T, s->gp_theta[p], tnew[p], s->sp.theta_alpha, s->sp.theta_beta)
               + a00_theta_gibbs_hastings(fa[p], fb[p], s->gp_theta[p], tnew[p]);
@@ -969,7 +971,8 @@ static int gs_prog_tau(bpa_sampler * s, int q)
   double sum = out[0];
   const long long * ol = reinterpret_cast<const long long *>(out);
   const bool bad = ol[4] != 0;
-  if (pq < 0 && s->sp.tau_alpha > 0) sum += (s->sp.tau_alpha - 1 - (s->sp.S - 1) + 1)*std::log(tnew/old) - s->sp.tau_beta*(tnew - old);
+  if (pq < 0 && s->sp.tau_alpha > 0) sum += a00_tau_prior_lnratio(smp::tau_kind(s->sp), s->sp.tau_alpha, s->sp.tau_beta, s->sp.S, old, tnew);
+  const int tk = smp::theta_kind(s->sp);
   gsm::GApply a{};
   a.set_tau_q = (uint32_t)q; a.tau_new = tnew; a.nprop = 1;
   double oldtheta[3], Cn[3] = {0, 0, 0};
@@ -981,13 +984,13 @@ static int gs_prog_tau(bpa_sampler * s, int q)
     if (bad || !s->gp_ok) { sum = NAN; continue; }
     double a1, b1, a1o, b1o;
     Cn[j] = (double)ol[1 + j]*(1.0/1099511627776.0);
-    a00_theta_conditional_invgamma(s->sp.theta_alpha, s->sp.theta_beta, k, Cn[j], &a1, &b1);
-    a00_theta_conditional_invgamma(s->sp.theta_alpha, s->sp.theta_beta, k, s->gp_T[p], &a1o, &b1o);
+    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, Cn[j], &a1, &b1);
+    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, s->gp_T[p], &a1o, &b1o);
     if (!(a1 == a1 && a1o == a1o)) { sum = NAN; continue; }
     const double g = a00_bpp_rndgamma(&gz, a1);
     const double tn = 1.0/(g/b1);
     sum += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-         + ((s->sp.theta_alpha - 1)*std::log(tn/to) - s->sp.theta_beta*(tn - to))
+         + a00_theta_prior_lnratio(tk, s->sp.theta_alpha, s->sp.theta_beta, to, tn)
          + (k*(std::log(2.0/tn) - std::log(2.0/to)) - (Cn[j]/tn - s->gp_T[p]/to));
     s->gp_theta[p] = tn;
   }
@@ -1013,6 +1016,7 @@ static int gs_prog_mix(bpa_sampler * s)
   const int npop = s->sp.npop;
   const double lnc = s->sp.ft_mix*a00_bpp_rnd_symmetrical(&gz), c = std::exp(lnc);
   double oldtheta[smp::MAXPOP], lnacc_theta = 0;
+  const int tk = smp::theta_kind(s->sp);
   for (int p = 0; p < npop; ++p) oldtheta[p] = s->gp_theta[p];
   for (int p = 0; p < npop; ++p)
   {
@@ -1021,13 +1025,13 @@ static int gs_prog_mix(bpa_sampler * s)
     if (!s->gp_ok) { lnacc_theta = NAN; continue; }
     double a1, b1, a1o, b1o;
     const double Ts = s->gp_T[p]*c;
-    a00_theta_conditional_invgamma(s->sp.theta_alpha, s->sp.theta_beta, k, Ts, &a1, &b1);
-    a00_theta_conditional_invgamma(s->sp.theta_alpha, s->sp.theta_beta, k, Ts/c, &a1o, &b1o);
+    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, Ts, &a1, &b1);
+    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, Ts/c, &a1o, &b1o);
     if (!(a1 == a1 && a1o == a1o)) { lnacc_theta = NAN; continue; }
     const double g = a00_bpp_rndgamma(&gz, a1);
     const double tn = 1.0/(g/b1);
     lnacc_theta += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-                 + ((s->sp.theta_alpha - 1)*std::log(tn/to) - s->sp.theta_beta*(tn - to))
+                 + a00_theta_prior_lnratio(tk, s->sp.theta_alpha, s->sp.theta_beta, to, tn)
                  + (k*(std::log(2.0/tn) - std::log(2.0/to)) - (Ts/tn - s->gp_T[p]/to));
     s->gp_theta[p] = tn;
   }
@@ -1045,7 +1049,7 @@ static int gs_prog_mix(bpa_sampler * s)
   const int root = npop - 1;
   double lnacc = out[0] + (double)(s->sp.S - 1)*lnc;
   if (s->sp.tau_alpha > 0)
-    lnacc += (s->sp.tau_alpha - 1)*lnc - s->sp.tau_beta*(s->gp_tau[root]*c - s->gp_tau[root]) - (double)(s->sp.S - 2)*lnc;
+    lnacc += a00_mix_tau_prior_lnratio(smp::tau_kind(s->sp), s->sp.tau_alpha, s->sp.tau_beta, s->sp.S, lnc, s->gp_tau[root], s->gp_tau[root]*c);
   lnacc += lnacc_theta;
   const bool acc = lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc);
   gs_declog("mix", 0, lnacc, acc);
@@ -1090,8 +1094,12 @@ template <int PHASE>
 static int gs_dec_launch(bpa_sampler * s, int q, int next)
 {
   bpa_engine * e = s->eng;
-  hipLaunchKernelGGL((gsm::gdec_kernel<PHASE>), dim3(1), dim3(64), sizeof(smp2::WgBase), e->stream, s->g_dst.p, (const double *)s->g_dsum.p, s->sp,
-                     gs_theta_mask(s), q, next, s->epoch, s->flag.p, s->counters.p, s->taus.p);
+  if (smp::theta_kind(s->sp))
+    hipLaunchKernelGGL((gsm::gdec_kernel<PHASE, 1>), dim3(1), dim3(64), sizeof(smp2::WgBase), e->stream, s->g_dst.p, (const double *)s->g_dsum.p, s->sp,
+                       gs_theta_mask(s), q, next, s->epoch, s->flag.p, s->counters.p, s->taus.p);
+  else
+    hipLaunchKernelGGL((gsm::gdec_kernel<PHASE, 0>), dim3(1), dim3(64), sizeof(smp2::WgBase), e->stream, s->g_dst.p, (const double *)s->g_dsum.p, s->sp,
+                       gs_theta_mask(s), q, next, s->epoch, s->flag.p, s->counters.p, s->taus.p);
   HIPCHK(hipGetLastError());
   s->launches++;
   return 1;

@@ -50,6 +50,7 @@ struct a00_driver
   double ft_gage, ft_gspr, ft_tau, ft_mix;
   double tau_alpha, tau_beta;           /* gamma prior on the root tau (0,0: flat) */
   double theta_alpha, theta_beta, ft_theta;   /* gamma prior on every theta (alpha 0: thetas fixed, no THETA steps) */
+  int theta_kind, tau_kind;              /* A00_PRIOR_GAMMA (0, the default) / A00_PRIOR_INVGAMMA of the two priors (a00_set_prior_kinds) */
   int has_theta[A00_MAXPOP];
   double l2t[A00_MAXPOP], l2t_of[A00_MAXPOP];   /* log(2/theta_p) and the theta it belongs to (tree_logpr_stats) */
   double * s_logpr;                     /* proposed MSC density per slot */
@@ -413,6 +414,27 @@ int a00_set_tip_species(a00_driver_t * d, unsigned i, const int * species)
 void a00_set_tau_prior(a00_driver_t * d, double alpha, double beta) { d->tau_alpha = alpha; d->tau_beta = beta; }
 void a00_set_theta_prior(a00_driver_t * d, double alpha, double beta, double finetune)
 { d->theta_alpha = alpha; d->theta_beta = beta; d->ft_theta = finetune; }
+void a00_set_prior_kinds(a00_driver_t * d, int theta_kind, int tau_kind)
+{
+  d->theta_kind = theta_kind == A00_PRIOR_INVGAMMA ? A00_PRIOR_INVGAMMA : A00_PRIOR_GAMMA;
+  d->tau_kind = tau_kind == A00_PRIOR_INVGAMMA ? A00_PRIOR_INVGAMMA : A00_PRIOR_GAMMA;
+}
+double a00_prior_piece(int which, int kind, double a, double b, const double * x)
+{
+  double a1 = NAN, b1 = NAN;
+  switch (which)
+  {
+    case 0: return a00_theta_prior_lnratio(kind, a, b, x[0], x[1]);
+    case 1: return a00_tau_prior_lnratio(kind, a, b, (int)x[0], x[1], x[2]);
+    case 2: return a00_mix_tau_prior_lnratio(kind, a, b, (int)x[0], x[1], x[2], x[3]);
+    case 3: return a00_theta_lnacc_kind(kind, (long)x[0], x[1], x[2], x[3], a, b);
+    case 4: a00_theta_conditional_kind(kind, a, b, (long)x[0], x[1], &a1, &b1); return a1;
+    case 5: a00_theta_conditional_kind(kind, a, b, (long)x[0], x[1], &a1, &b1); return b1;
+    case 6: return a00_theta_lnacc((long)x[0], x[1], x[2], x[3], a, b);
+    case 7: return a00_invgamma_logpdf(x[0], a, b);
+  }
+  return NAN;
+}
 unsigned a00_get_thetas(const a00_driver_t * d, double * theta)
 {
   int p;
@@ -426,7 +448,7 @@ unsigned a00_get_thetas(const a00_driver_t * d, double * theta)
 static double root_tau_prior_ratio(const a00_driver_t * d, double oldt, double newt)
 {
   if (!(d->tau_alpha > 0)) return 0;
-  return (d->tau_alpha - 1 - (d->S - 1) + 1)*log(newt/oldt) - d->tau_beta*(newt - oldt);
+  return a00_tau_prior_lnratio(d->tau_kind, d->tau_alpha, d->tau_beta, d->S, oldt, newt);
 }
 
 void a00_set_finetune(a00_driver_t * d, double gage, double gspr, double tau, double mix)
@@ -836,7 +858,7 @@ static int theta_step_all(a00_driver_t * d)
   {
     double lnacc;
     if (!d->has_theta[p]) continue;
-    lnacc = sum[p] + ((d->theta_alpha - 1)*log(tnew[p]/d->theta[p]) - d->theta_beta*(tnew[p] - d->theta[p]));
+    lnacc = sum[p] + a00_theta_prior_lnratio(d->theta_kind, d->theta_alpha, d->theta_beta, d->theta[p], tnew[p]);
     d->proposals++;
     { const int acc_ = tnew[p] > 0 && accept(d, -1, lnacc, uacc[p]); declog("theta", p, lnacc, uacc[p], acc_); if (acc_) { d->accepted++; d->theta[p] = tnew[p]; } }
   }
@@ -899,7 +921,7 @@ static int theta_step_gibbs(a00_driver_t * d)
   {
     fa[p] = fb[p] = NAN;
     if (!d->has_theta[p] || bad || slide[p]) continue;
-    a00_theta_conditional_invgamma(d->theta_alpha, d->theta_beta, (long)ksum[p], d->run_T[p], &fa[p], &fb[p]);
+    a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, (long)ksum[p], d->run_T[p], &fa[p], &fb[p]);
     if (fa[p] == fa[p]) tnew[p] = 1/(a00_bpp_rndgamma(&d->gz, fa[p])/fb[p]);
   }
   for (p = 0; p < d->npop; ++p)
@@ -910,7 +932,9 @@ static int theta_step_gibbs(a00_driver_t * d)
     T = d->run_T[p];
     if (!bad)
     {
-      if (slide[p]) lnacc = a00_theta_lnacc((long)ksum[p], T, d->theta[p], tnew[p], d->theta_alpha, d->theta_beta);
+      if (slide[p]) lnacc = a00_theta_lnacc_kind(d->theta_kind, (long)ksum[p], T, d->theta[p], tnew[p], d->theta_alpha, d->theta_beta);
+      else if (fa[p] == fa[p] && d->theta_kind == A00_PRIOR_INVGAMMA)
+        lnacc = tnew[p] == tnew[p] ? 0.0 : NAN;          /* a draw from the conditional itself: accepted, no acceptance number (stree.c:3822) */
       else if (fa[p] == fa[p])
         lnacc = a00_theta_lnacc((long)ksum[p], T, d->theta[p], tnew[p], d->theta_alpha, d->theta_beta)
               + a00_theta_gibbs_hastings(fa[p], fb[p], d->theta[p], tnew[p]);
@@ -1009,13 +1033,13 @@ static int tau_step(a00_driver_t * d, int q)
       if (!d->has_theta[p]) continue;
       if (bad || !d->run_ok) { sum = NAN; continue; }
       Cn = (double)cnew[j]*(1.0/1099511627776.0);
-      a00_theta_conditional_invgamma(d->theta_alpha, d->theta_beta, k, Cn, &a1, &b1);
-      a00_theta_conditional_invgamma(d->theta_alpha, d->theta_beta, k, d->run_T[p], &a1o, &b1o);
+      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, Cn, &a1, &b1);
+      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, d->run_T[p], &a1o, &b1o);
       if (!(a1 == a1 && a1o == a1o)) { sum = NAN; continue; }
       g = a00_bpp_rndgamma(&d->gz, a1);
       tn = 1.0/(g/b1);
       sum += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-           + ((d->theta_alpha - 1)*log(tn/to) - d->theta_beta*(tn - to))
+           + a00_theta_prior_lnratio(d->theta_kind, d->theta_alpha, d->theta_beta, to, tn)
            + (k*(log(2.0/tn) - log(2.0/to)) - (Cn/tn - d->run_T[p]/to));
       d->theta[p] = tn;
     }
@@ -1067,13 +1091,13 @@ static int mix_step(a00_driver_t * d)
       if (!d->has_theta[p]) continue;
       if (!d->run_ok) { lnacc_theta = NAN; continue; }
       Ts = d->run_T[p]*c;
-      a00_theta_conditional_invgamma(d->theta_alpha, d->theta_beta, k, Ts, &a1, &b1);
-      a00_theta_conditional_invgamma(d->theta_alpha, d->theta_beta, k, Ts/c, &a1o, &b1o);
+      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, Ts, &a1, &b1);
+      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, Ts/c, &a1o, &b1o);
       if (!(a1 == a1 && a1o == a1o)) { lnacc_theta = NAN; continue; }
       g = a00_bpp_rndgamma(&d->gz, a1);
       tn = 1.0/(g/b1);
       lnacc_theta += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-                   + ((d->theta_alpha - 1)*log(tn/to) - d->theta_beta*(tn - to))
+                   + a00_theta_prior_lnratio(d->theta_kind, d->theta_alpha, d->theta_beta, to, tn)
                    + (k*(log(2.0/tn) - log(2.0/to)) - (Ts/tn - d->run_T[p]/to));
       d->theta[p] = tn;
     }
@@ -1105,7 +1129,7 @@ static int mix_step(a00_driver_t * d)
   for (i = 0; i < d->nloci; ++i) sum += (d->b_lnl[i] - d->trees[i].lnl) + d->p_delta[i];
   lnacc = sum + (double)(d->S - 1)*lnc;
   if (d->tau_alpha > 0)                    /* all taus scale together: the Dirichlet part is unchanged */
-    lnacc += (d->tau_alpha - 1)*lnc - d->tau_beta*(d->tau[d->npop-1] - oldtau[d->npop-1]) - (double)(d->S - 2)*lnc;
+    lnacc += a00_mix_tau_prior_lnratio(d->tau_kind, d->tau_alpha, d->tau_beta, d->S, lnc, oldtau[d->npop-1], d->tau[d->npop-1]);
   lnacc += lnacc_theta;
   d->proposals++;
   acc_ = accept(d, -1, lnacc, uacc);

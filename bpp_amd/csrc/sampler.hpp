@@ -57,7 +57,9 @@ struct Species
   uint16_t anc[MAXPOP];                    // bit q: q is p or an ancestor of p
   double   ft_gage, ft_gspr, ft_tau, ft_mix, tau_alpha, tau_beta;
   double   ft_theta, theta_alpha, theta_beta;
-  int32_t  program_moves, pad_;            // persistent kernel with BPP's proposal kernel: THETA / TAU / MIX as the program runs them (bpa_sampler_set_program_moves)
+  int32_t  program_moves, prior_kinds;     // persistent kernel with BPP's proposal kernel: THETA / TAU / MIX as the program runs them (bpa_sampler_set_program_moves)
+                                           //   prior_kinds: bit 0 the theta prior's family, bit 1 the root tau's (0 gamma, 1 inverse gamma: bpa_sampler_set_prior_kinds;
+                                           //   the generic, big-tree and one-launch-per-step samplers — the persistent kernel has the gamma forms only)
   double   theta_slide_prob;               //   share of sliding-window THETA proposals, the rest Gibbs draws
 };
 
@@ -971,6 +973,9 @@ __global__ void __launch_bounds__(BS) sweep_kernel(const Args A)
   }
 }
 
+__device__ __host__ __forceinline__ int theta_kind(const Species & sp) { return sp.prior_kinds & 1; }
+__device__ __host__ __forceinline__ int tau_kind(const Species & sp) { return (sp.prior_kinds >> 1) & 1; }
+
 // the single decision of an all-loci step (tau_step / mix_step of a00_driver.c; stree.c:6280,
 // prop_mixing.c:203-205): flag := epoch when REJECTED; on acceptance the device-resident taus follow
 __device__ void decide(double lnacc, double u, uint32_t epoch, uint32_t * flag,
@@ -984,7 +989,7 @@ __device__ void decide(double lnacc, double u, uint32_t epoch, uint32_t * flag,
   {
     const double old = taus[MAXPOP + theta_p];
     tnew = reflect(old + sp.ft_theta*(win_u - 0.5), 0.0, 999.0);
-    lnacc += (sp.theta_alpha - 1)*log(tnew/old) - sp.theta_beta*(tnew - old);
+    lnacc += a00_theta_prior_lnratio(theta_kind(sp), sp.theta_alpha, sp.theta_beta, old, tnew);
     valid = tnew > 0;
   }
   else if (tau_q >= 0)
@@ -992,13 +997,13 @@ __device__ void decide(double lnacc, double u, uint32_t epoch, uint32_t * flag,
     const int pq = sp.parent[tau_q];
     const double old = taus[tau_q], lo = fmax(taus[sp.left[tau_q]], taus[sp.right[tau_q]]), hi = pq >= 0 ? taus[pq] : 999.0;
     tnew = reflect(old + sp.ft_tau*(win_u - 0.5), lo, hi);
-    if (pq < 0 && sp.tau_alpha > 0) lnacc += (sp.tau_alpha - 1 - (sp.S - 1) + 1)*log(tnew/old) - sp.tau_beta*(tnew - old);
+    if (pq < 0 && sp.tau_alpha > 0) lnacc += a00_tau_prior_lnratio(tau_kind(sp), sp.tau_alpha, sp.tau_beta, sp.S, old, tnew);
   }
   else
   {
     lnacc += (double)(sp.S - 1)*mix_lnc;
     if (sp.tau_alpha > 0)
-      lnacc += (sp.tau_alpha - 1)*mix_lnc - sp.tau_beta*(taus[root]*mix_c - taus[root]) - (double)(sp.S - 2)*mix_lnc;
+      lnacc += a00_mix_tau_prior_lnratio(tau_kind(sp), sp.tau_alpha, sp.tau_beta, sp.S, mix_lnc, taus[root], taus[root]*mix_c);
   }
   const bool accept = valid && (lnacc >= 0 || u < exp(lnacc));
   counters[0] += 1; counters[1] += accept ? 1u : 0u;
@@ -1076,7 +1081,7 @@ __global__ void __launch_bounds__(1024) theta_sum_decide_kernel(const int8_t * _
     if (threadIdx.x == 0 && sums_out) sums_out[p] = total;
   }
   if (threadIdx.x || !decide_on) return;
-  const double lnacc = total + ((sp.theta_alpha - 1)*log(tnew/told) - sp.theta_beta*(tnew - told));
+  const double lnacc = total + a00_theta_prior_lnratio(theta_kind(sp), sp.theta_alpha, sp.theta_beta, told, tnew);
   const bool accept = tnew > 0 && (lnacc >= 0 || ta.uacc[p] < exp(lnacc));
   atomicAdd(&counters[0], 1u); if (accept) atomicAdd(&counters[1], 1u);
   if (accept) { taus[MAXPOP + p] = tnew; taus[2*MAXPOP + p] = l2t_new; }
@@ -1220,6 +1225,7 @@ struct bpa_sampler
   a00_rng_t grng = 0;
   unsigned long seed = 0, launches = 0, sweeps = 0;
   bool uploaded = false;
+  bool started = false;                 // bpa_sampler_initialize has run (the calls that come before it refuse from then on, whatever is invalidated later)
   uint32_t h_counters[4] = {0, 0, 0, 0};   // all-loci proposals / accepted (+ of those: THETA Gibbs draws / accepted) at the last invalidation (re-uploaded)
   bool host_current = false;            // the host copies (h_trees / g_trees, g_sm_host) hold the device's state: set by a download, cleared by iterate
   // ---- the persistent iteration kernel (sweep2.hpp): one GPU, loci that fit the sweep kernel, root = the last node
@@ -1484,6 +1490,24 @@ extern "C" int bpa_sampler_set_program_moves(bpa_sampler_t * s, int on, double s
   if (on) s->sp.theta_slide_prob = slide_prob;
   // (the persistent kernel's form — with or without a control wave — is chosen at upload)
   if (s->uploaded && s->v2_ok && v2_wants_prog(s) != s->v2_prog) return sampler_invalidate(s);
+  return 1;
+}
+
+// the families of the two priors (Species::prior_kinds).  Where they are honoured: every decision of the generic and the big-tree
+// sampler (both move sets) and of the one-launch-per-step sampler (smp::decide, theta_sum_decide_kernel).  The persistent kernel
+// has the gamma forms only, and so has whatever runs it or exchanges sums for it.
+extern "C" int bpa_sampler_set_prior_kinds(bpa_sampler_t * s, int theta_kind, int tau_kind)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if ((theta_kind != BPA_PRIOR_GAMMA && theta_kind != BPA_PRIOR_INVGAMMA) || (tau_kind != BPA_PRIOR_GAMMA && tau_kind != BPA_PRIOR_INVGAMMA))
+    return fail("bpa_sampler_set_prior_kinds: BPA_PRIOR_GAMMA or BPA_PRIOR_INVGAMMA");
+  if (s->comp) return fail("bpa_sampler_set_prior_kinds: loci of several kinds have the gamma priors only (one sampler per kind of locus takes the call)");
+  if (s->uploaded || s->started) return fail("bpa_sampler_set_prior_kinds: before bpa_sampler_initialize (as a00_set_prior_kinds)");
+  if (s->allreduce || s->p2p) return fail("bpa_sampler_set_prior_kinds: several ranks have the gamma priors only (an all-reduce callback or the mailboxes are installed: run the loci on one rank)");
+  // (which kernel runs the loci is settled at upload; loci that fit the persistent kernel get it unless one of these holds)
+  if (!(s->generic || s->big || s->env_v1 || s->env_trace))
+    return fail("bpa_sampler_set_prior_kinds: the persistent kernel has the gamma priors only: BPA_SMP_GENERIC=1 or BPA_SMP_V1=1 at creation");
+  s->sp.prior_kinds = (theta_kind == BPA_PRIOR_INVGAMMA ? 1 : 0) | (tau_kind == BPA_PRIOR_INVGAMMA ? 2 : 0);
   return 1;
 }
 
@@ -2243,6 +2267,7 @@ extern "C" int bpa_sampler_initialize(bpa_sampler_t * s)
 {
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
   if (s->comp) return comp_run(s, 0, 0);
+  s->started = true;
   if (!sampler_upload(s)) return 0;
   s->host_current = false;
   if (s->big) return gb_initialize(s);
@@ -2286,6 +2311,7 @@ extern "C" int bpa_sampler_set_allreduce(bpa_sampler_t * s, bpa_allreduce_fn fn,
 {
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
   if (s->comp) return comp_set_allreduce(s, fn, ctx, device_sum, first_locus);
+  if (fn && s->sp.prior_kinds) return fail("bpa_sampler_set_allreduce: several ranks have the gamma priors only (bpa_sampler_set_prior_kinds chose an inverse gamma)");
   s->allreduce = fn; s->allreduce_ctx = ctx; s->sum_ext = device_sum;
   if (first_locus != s->locus_offset)
   {
@@ -2530,6 +2556,7 @@ extern "C" int bpa_sampler_set_p2p(bpa_sampler_t * s, bpa_p2p_t * p, unsigned fi
   if (p && (!p->connected || p->eng != s->eng)) return fail("bpa_sampler_set_p2p: connect the exchange first (same engine)");
   if (p && p->nmax < 16u) return fail("bpa_sampler_set_p2p: the mailboxes must hold at least 16 values");
   // only the persistent kernel reads the mailboxes: a generic or big-tree sampler would decide from its own shard's sums
+  if (p && s->sp.prior_kinds) return fail("bpa_sampler_set_p2p: several ranks have the gamma priors only (bpa_sampler_set_prior_kinds chose an inverse gamma)");
   if (p && (s->generic || s->big)) return fail("bpa_sampler_set_p2p: the in-kernel exchange needs the persistent kernel (JC69 loci of <= 8 tips, <= 64 patterns); use bpa_sampler_set_allreduce");
   if (!sampler_invalidate(s)) return 0;
   s->p2p = p;

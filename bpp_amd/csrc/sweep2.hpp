@@ -439,8 +439,10 @@ __device__ __forceinline__ double prog_lcg(uint32_t & z)                   // a0
 }
 // draw_gammas' way back (below; about one block in a hundred): the block's variates one after the other, the stream from the
 // block's start.  A call for the same reason as prog_lgamma_small (a00_bpp_rndgamma: square roots, logarithms, pow).
+// (The one-wave gsm::gdec_kernel has registers to spare: its inverse-gamma instances take the body inline — no call, so no
+// callee-saved register goes to scratch.)
 struct GammasRedo { double g; uint32_t z; };
-__device__ __noinline__ GammasRedo prog_gammas_redo(uint32_t z, uint32_t lane, unsigned long long list, int n, uint32_t want, double shape, double g)
+__device__ __forceinline__ GammasRedo prog_gammas_redo_inline(uint32_t z, uint32_t lane, unsigned long long list, int n, uint32_t want, double shape, double g)
 {
   for (int i = 0; i < n; ++i)
   {
@@ -451,6 +453,10 @@ __device__ __noinline__ GammasRedo prog_gammas_redo(uint32_t z, uint32_t lane, u
   }
   return GammasRedo{g, z};
 }
+__device__ __noinline__ GammasRedo prog_gammas_redo(uint32_t z, uint32_t lane, unsigned long long list, int n, uint32_t want, double shape, double g)
+{
+  return prog_gammas_redo_inline(z, lane, list, n, want, shape, g);
+}
 // gamma(shape, 1) variates for the populations of `list` (4 bits each, n entries) whose bit is set in `want`, from the global
 // stream in list order, exactly the numbers a00_bpp_rndgamma (legacy_rndgamma, random.c:240-275: Marsaglia-Tsang on the
 // polar normal) gives one after the other — but side by side: WHICH uniforms a variate takes is settled by cheap
@@ -459,6 +465,7 @@ __device__ __noinline__ GammasRedo prog_gammas_redo(uint32_t z, uint32_t lane, u
 // lane p then does population p's square root, logs and test.  A variate that does not pass (about one draw in a
 // hundred) sends everybody back to the start of the block and through the draws one after the other.
 // shape: lane p.  xarg / xlog: a number per lane >= 16 whose log rides along in the same call.  Returns the variate on lane p.
+template <int TK = 0>
 __device__ __forceinline__ double draw_gammas(uint32_t & zz, uint32_t lane, unsigned long long list, int n, uint32_t want, double shape, double xarg, double & xlog)
 {
   const uint32_t z0 = zz;
@@ -497,7 +504,7 @@ __device__ __forceinline__ double draw_gammas(uint32_t & zz, uint32_t lane, unsi
   }
   if (!scan_ok || __any(mine && !ok))
   {
-    const GammasRedo r = prog_gammas_redo(z0, lane, list, n, want, shape, g);
+    const GammasRedo r = TK == 1 ? prog_gammas_redo_inline(z0, lane, list, n, want, shape, g) : prog_gammas_redo(z0, lane, list, n, want, shape, g);
     z = r.z; g = r.g;
   }
   zz = z;
@@ -506,6 +513,9 @@ __device__ __forceinline__ double draw_gammas(uint32_t & zz, uint32_t lane, unsi
 // A re-drawn theta's part of ln(acceptance ratio) (tau_step / mix_step of a00_driver.c; stree.c:5840-5990, prop_mixing.c:272-425), lane p < 16 for population p:
 //   [invgamma(theta | old fit) - invgamma(theta' | new fit)] + [gamma prior ratio] + [k (log 2/theta' - log 2/theta) - (T'/theta' - T/theta)]
 // Its four logs and four quotients are taken side by side: lane p + 16 m computes piece m.  l2t_new = log(2/theta') comes out too.
+// TK: the theta prior's family (0 gamma, 1 inverse gamma: a00_theta_prior_lnratio of bpp_amd_host.h), a compile-time parameter of
+// the decisions below — the persistent kernel calls the gamma forms, gsm::gdec_kernel has instances of both.
+template <int TK = 0>
 __device__ __forceinline__ double redraw_ratio(const WgBase & wg, uint32_t lane, double kk, double tn, double a1, double b1, double c1, double Tn,
                                                double ao, double bo, double co, double Told, double & l2t_new)
 {
@@ -522,7 +532,16 @@ __device__ __forceinline__ double redraw_ratio(const WgBase & wg, uint32_t lane,
   l2t_new = L2;
   const double l2t_old = wg.tau[2*MAXPOP + (p < MAXPOP ? p : 0)];
   const double anew = (c1 + (-a1 - 1)*L0) - r0, aold = (co + (-ao - 1)*L3) - r3;
+  if (TK == 1) return (aold - anew) + ((-wg.sp.theta_alpha - 1)*L1 - wg.sp.theta_beta*(1/tn - 1/to_p)) + (kk*(L2 - l2t_old) - (r1 - r2));
   return (aold - anew) + ((wg.sp.theta_alpha - 1)*L1 - wg.sp.theta_beta*(tn - to_p)) + (kk*(L2 - l2t_old) - (r1 - r2));
+}
+// the inverse gamma a theta is drawn from given (k, T): the fit to the conditional under the gamma prior, the conditional
+// itself — (a + k, b + T) — under the inverse gamma (a00_theta_conditional_kind)
+template <int TK>
+__device__ __forceinline__ void theta_conditional(const WgBase & wg, double k, double T, double * a1, double * b1)
+{
+  if (TK == 1) { *a1 = wg.sp.theta_alpha + (long)k; *b1 = wg.sp.theta_beta + T; }
+  else a00_theta_conditional_invgamma_fast(wg.sp.theta_alpha, wg.sp.theta_beta, (long)k, T, a1, b1);
 }
 
 // THETA (theta_step_gibbs of a00_driver.c): the sums the exchange brought (xtot[0 .. 2 n): k_p, T_p of the populations of the
@@ -532,6 +551,7 @@ __device__ __forceinline__ double redraw_ratio(const WgBase & wg, uint32_t lane,
 // thetas in tau[] (a TAU decision follows at once).  z: the global stream.
 // tau_q >= 0: the fits the TAU decision that follows at once will want (populations tau_q and its children against the sums
 // xtot[tau_base + 2 .. 4]) are made in the same call, on lanes 16 + p, and left in rd[p].a / .b.
+template <int TK = 0>
 __device__ __forceinline__ uint32_t prog_theta_decide(uint32_t z, uint32_t theta_mask, uint32_t slidem, double tslide, int apply_now, int tau_q = -1, int tau_base = 0)
 {
   WgBase & wg = wg_base();
@@ -555,7 +575,7 @@ __device__ __forceinline__ uint32_t prog_theta_decide(uint32_t z, uint32_t theta
       const double kk = __shfl(runK, (int)pl16, 64);
       const double Cn = taff ? wg.xtot[tau_base + ((int)pl16 == tau_q ? 2 : (int)pl16 == tcl ? 3 : 4)] : qnan;
       double fa = qnan, fb = qnan;
-      if (mine || (taff && Cn == Cn)) a00_theta_conditional_invgamma_fast(wg.sp.theta_alpha, wg.sp.theta_beta, (long)kk, mine ? runT : Cn, &fa, &fb);
+      if (mine || (taff && Cn == Cn)) theta_conditional<TK>(wg, kk, mine ? runT : Cn, &fa, &fb);
       if (mine) { fitA = fa; fitB = fb; }
       if (role == 1u) { wg.rd[pl16].a = fa; wg.rd[pl16].b = fb; }
     }
@@ -563,7 +583,7 @@ __device__ __forceinline__ uint32_t prog_theta_decide(uint32_t z, uint32_t theta
     const uint32_t gm = theta_mask & ~slidem & fitm;
     double xl;
     const double s_fa = __shfl(fitA, (int)pl16, 64), s_fb = __shfl(fitB, (int)pl16, 64);
-    const double g = draw_gammas(z, lane, 0xfedcba9876543210ull, npop, gm, fitA, role == 1u ? s_fb : s_fa, xl);
+    const double g = draw_gammas<TK>(z, lane, 0xfedcba9876543210ull, npop, gm, fitA, role == 1u ? s_fb : s_fa, xl);
     {
       const double lb = __shfl(xl, 16 + (int)pl16, 64), la = __shfl(xl, 32 + (int)pl16, 64);
       if (lane < 16u && fitA == fitA) fitC = fitA*lb - lgamma_with_log(fitA, la);
@@ -581,8 +601,17 @@ __device__ __forceinline__ uint32_t prog_theta_decide(uint32_t z, uint32_t theta
       const double l2t_old = wg.tau[2*MAXPOP + (p < MAXPOP ? p : 0)];
       if (mine && tn == tn)
       {
+        if (TK == 1)
+        {
+          // the window against the inverse-gamma prior; a Gibbs draw comes from the conditional itself: accepted, no number drawn (stree.c:3822)
+          lnacc_p = (runK*(L2 - l2t_old) - (r0 - r1)) + ((-wg.sp.theta_alpha - 1)*L1 - wg.sp.theta_beta*(r2 - r3));
+          if ((gm >> pl16) & 1u) lnacc_p = 0.0;
+        }
+        else
+        {
         lnacc_p = (runK*(L2 - l2t_old) - (r0 - r1)) + ((wg.sp.theta_alpha - 1)*L1 - wg.sp.theta_beta*(tn - to_p));
         if ((gm >> pl16) & 1u) lnacc_p += (-fitA - 1)*L3 - fitB*(r3 - r2);
+        }
       }
       e_p = exp(lnacc_p);
       l2_p = L2;
@@ -615,6 +644,7 @@ __device__ __forceinline__ uint32_t prog_theta_decide(uint32_t z, uint32_t theta
 // (xtot[base], + the coarse companion) and the new T2h sums of q and its two children (xtot[base + 2 .. 4]); each of their
 // thetas is re-drawn from the fit to (k, new sum) and enters the ratio against the fit to the current sums (pf).
 // lnacc0 = the window's prior term.  Leaves dec.acc_step / rd_mask / lnacc_step and rd[] (installed by the caller on acceptance).
+template <int TK = 0>
 __device__ __forceinline__ uint32_t prog_tau_decide(uint32_t z, uint32_t theta_mask, int q, int base, double lnacc0, bool prefit = false)
 {
   WgBase & wg = wg_base();
@@ -630,15 +660,15 @@ __device__ __forceinline__ uint32_t prog_tau_decide(uint32_t z, uint32_t theta_m
   const double Cn = have ? wg.xtot[base + ((int)lane == q ? 2 : (int)lane == cl ? 3 : 4)] : qnan;
   double fa = qnan, fb = qnan, tn = qnan, l2t = 0;
   if (prefit) { if (have && Cn == Cn) { fa = wg.rd[pl16].a; fb = wg.rd[pl16].b; } }           // (made with THETA's: prog_theta_decide)
-  else if (have && Cn == Cn) a00_theta_conditional_invgamma_fast(wg.sp.theta_alpha, wg.sp.theta_beta, (long)f.k, Cn, &fa, &fb);
+  else if (have && Cn == Cn) theta_conditional<TK>(wg, f.k, Cn, &fa, &fb);
   const uint32_t rd_mask = (uint32_t)__ballot(have && fa == fa && f.a == f.a) & 0xffffu;
   double xl;
   const double s_fa = __shfl(fa, (int)pl16, 64), s_fb = __shfl(fb, (int)pl16, 64);
-  const double g = draw_gammas(z, lane, (unsigned long long)q | ((unsigned long long)cl << 4) | ((unsigned long long)cr << 8), 3, rd_mask, fa, role == 1u ? s_fb : s_fa, xl);
+  const double g = draw_gammas<TK>(z, lane, (unsigned long long)q | ((unsigned long long)cl << 4) | ((unsigned long long)cr << 8), 3, rd_mask, fa, role == 1u ? s_fb : s_fa, xl);
   const double lb = __shfl(xl, 16 + (int)pl16, 64), la = __shfl(xl, 32 + (int)pl16, 64);
   const double c1 = fa*lb - lgamma_with_log(fa, la);
   if (lane < 16u && ((rd_mask >> pl16) & 1u)) tn = 1.0/(g/fb);
-  const double x = redraw_ratio(wg, lane, f.k, tn, fa, fb, c1, Cn, f.a, f.b, f.c, f.T, l2t);
+  const double x = redraw_ratio<TK>(wg, lane, f.k, tn, fa, fb, c1, Cn, f.a, f.b, f.c, f.T, l2t);
   for (int j = 0; j < 3; ++j)
   {
     const int p = j == 0 ? q : j == 1 ? cl : cr;
@@ -657,6 +687,7 @@ __device__ __forceinline__ uint32_t prog_tau_decide(uint32_t z, uint32_t theta_m
 // MIX: every theta from the fit to its conditional given the SCALED trees (k, c T) (mix_step of a00_driver.c;
 // prop_mixing.c: Cjstar / c) — nothing of it depends on the loci's sums, so the caller runs it between its workgroup's
 // arrival at the exchange and the totals'.  Leaves rd[], dec.rd_mask and dec.lnacc_theta.
+template <int TK = 0>
 __device__ __forceinline__ uint32_t prog_mix_redraw(uint32_t z, uint32_t theta_mask, double mix_c)
 {
   WgBase & wg = wg_base();
@@ -669,16 +700,16 @@ __device__ __forceinline__ uint32_t prog_mix_redraw(uint32_t z, uint32_t theta_m
   const bool have = lane < 32u && pm < npop && ((theta_mask >> pm) & 1u) && run_ok;
   const double Ts = f.T*mix_c;
   double fa = qnan, fb = qnan, tn = qnan, l2t = 0;
-  if (have) a00_theta_conditional_invgamma_fast(wg.sp.theta_alpha, wg.sp.theta_beta, (long)f.k, role == 0u ? Ts : Ts/mix_c, &fa, &fb);
+  if (have) theta_conditional<TK>(wg, f.k, role == 0u ? Ts : Ts/mix_c, &fa, &fb);
   const double fao = __shfl(fa, 16 + pm, 64), fbo = __shfl(fb, 16 + pm, 64);
   const uint32_t rd_mask = (uint32_t)__ballot(lane < 16u && have && fa == fa && fao == fao) & 0xffffu;
   double xl;
   const double s_fa = __shfl(fa, pm, 64), s_fb = __shfl(fb, pm, 64);
-  const double g = draw_gammas(z, lane, 0xfedcba9876543210ull, npop, rd_mask, fa, role == 1u ? s_fb : role == 2u ? s_fa : fbo, xl);
+  const double g = draw_gammas<TK>(z, lane, 0xfedcba9876543210ull, npop, rd_mask, fa, role == 1u ? s_fb : role == 2u ? s_fa : fbo, xl);
   const double lb = __shfl(xl, 16 + pm, 64), la = __shfl(xl, 32 + pm, 64), lbo = __shfl(xl, 48 + pm, 64), lao = log(fao);
   const double c1 = fa*lb - lgamma_with_log(fa, la), co = fao*lbo - lgamma_with_log(fao, lao);
   if (lane < 16u && ((rd_mask >> pl16) & 1u)) tn = 1.0/(g/fb);
-  const double x = redraw_ratio(wg, lane, f.k, tn, fa, fb, c1, Ts, fao, fbo, co, f.T, l2t);
+  const double x = redraw_ratio<TK>(wg, lane, f.k, tn, fa, fb, c1, Ts, fao, fbo, co, f.T, l2t);
   double lnacc_theta = 0;
   for (int p = 0; p < npop; ++p)
     if ((theta_mask >> p) & 1u)

@@ -387,8 +387,19 @@ int  bpa_sampler_set_proposal_kernel(bpa_sampler_t *, int kind);
    a00_set_program_moves.                                                                                                */
 int  bpa_sampler_set_program_moves(bpa_sampler_t *, int on, double slide_prob);
 int  bpa_sampler_gibbs_counters(bpa_sampler_t *, unsigned long * proposals, unsigned long * accepted);
-void bpa_sampler_set_tau_prior(bpa_sampler_t *, double alpha, double beta);           /* a00_set_tau_prior */
-void bpa_sampler_set_theta_prior(bpa_sampler_t *, double alpha, double beta, double finetune); /* a00_set_theta_prior */
+void bpa_sampler_set_tau_prior(bpa_sampler_t *, double alpha, double beta);           /* a00_set_tau_prior: (alpha, beta) of the gamma or, bpa_sampler_set_prior_kinds, the inverse gamma */
+void bpa_sampler_set_theta_prior(bpa_sampler_t *, double alpha, double beta, double finetune); /* a00_set_theta_prior: likewise */
+/* The families of the two priors: BPP's 'thetaprior = gamma a b' / 'tauprior = gamma a b' (the default here) or its own
+   default, 'thetaprior = invgamma a b e' / 'tauprior = invgamma a b' (a00_set_prior_kinds; the arithmetic is in
+   bpp_amd_host.h).  Before bpa_sampler_initialize; 0 + bpa_last_error on refusal.  Honoured by the generic sampler (both
+   move sets, device- and host-decided), the big-tree sampler (both move sets) and the one-launch-per-step sampler.
+   Refused: the persistent kernel, which has the gamma priors only (loci that fit it get it: BPA_SMP_GENERIC=1 or
+   BPA_SMP_V1=1 at creation is the way out); loci of several kinds; a sampler with an all-reduce callback or mailboxes
+   installed (and installing one after an inverse gamma was chosen); a kind other than the two; a call after
+   bpa_sampler_initialize.  A sampler that never calls this runs exactly as it did.                                       */
+#define BPA_PRIOR_GAMMA    0
+#define BPA_PRIOR_INVGAMMA 1
+int  bpa_sampler_set_prior_kinds(bpa_sampler_t *, int theta_kind, int tau_kind);
 int  bpa_sampler_get_thetas(bpa_sampler_t *, double * theta); /* 2*species-1 entries; returns their number */
 int  bpa_sampler_get_taus(bpa_sampler_t *, double * tau);     /* 2*species-1 entries; returns their number */
 /* Several GPUs (threads.c:544-591): every rank samples its own loci with the same seed, so

@@ -270,6 +270,10 @@ static inline A00_HD double a00_invgamma_logpdf(double x, double a, double b)
   return a*log(b) - lgamma(a) + (-a - 1)*log(x) - b/x;
 }
 
+/* the two prior families of the thetas and of the root tau (gamma / inverse gamma) and every expression that depends on
+   the family: A00_HD functions like the ones above, in a header of their own */
+#include "bpp_amd_priors.h"
+
 /* gene tree of one locus: tips 0..tips-1, inner nodes after; the root node object stays
    the root (gtree.c:6129-6175), so pmatrix indices never collide */
 typedef struct a00_tree
@@ -351,12 +355,23 @@ void           a00_theta_conditional(double a, double b, long k, double T, doubl
 void           a00_theta_conditional_fast(double a, double b, long k, double T, double * a1b1);
 /* window widths of the four moves (defaults 0.004, 0.004, 0.001, 0.3) */
 void           a00_set_finetune(a00_driver_t *, double gage, double gspr, double tau, double mix);
-/* prior on the divergence times as BPP's 'tauprior = gamma a b': gamma(alpha, beta) on the root tau, the
-   others uniform below it (stree.c:5655-5657); alpha = 0 (default): flat */
+/* prior on the divergence times as BPP's 'tauprior = gamma a b' (or, a00_set_prior_kinds, 'tauprior = invgamma a b'):
+   gamma / inverse-gamma(alpha, beta) on the root tau, the others uniform below it (stree.c:5655-5672); alpha = 0
+   (default): flat */
 void           a00_set_tau_prior(a00_driver_t *, double alpha, double beta);
-/* thetas: BPP's 'thetaprior = gamma a b' with a sliding-window THETA step per population that can hold a
-   coalescence, after the gene-tree moves of every iteration; alpha = 0 (default): thetas stay fixed */
+/* thetas: BPP's 'thetaprior = gamma a b' (or, a00_set_prior_kinds, 'thetaprior = invgamma a b e') with a sliding-window
+   THETA step per population that can hold a coalescence, after the gene-tree moves of every iteration; alpha = 0
+   (default): thetas stay fixed */
 void           a00_set_theta_prior(a00_driver_t *, double alpha, double beta, double finetune);
+/* the families (alpha, beta) of the two calls above belong to: A00_PRIOR_GAMMA (default) or A00_PRIOR_INVGAMMA, the
+   program's default.  Honoured by THETA (window and Gibbs draw), TAU and MIX under either kernel.  An inverse-gamma Gibbs
+   step of THETA draws its gamma variate and nothing else.  Other values are taken as gamma.                           */
+void           a00_set_prior_kinds(a00_driver_t *, int theta_kind, int tau_kind);
+/* the pieces above as functions of the library (tests): which = 0 theta prior ratio (x: told, tnew), 1 root tau in TAU
+   (x: S, told, tnew), 2 root tau in MIX (x: S, lnc, told, tnew), 3 a00_theta_lnacc_kind (x: k, T, told, tnew),
+   4 / 5 a1 / b1 of a00_theta_conditional_kind (x: k, T), 6 a00_theta_lnacc itself (gamma; x as 3),
+   7 a00_invgamma_logpdf (x: the argument)                                                                             */
+double         a00_prior_piece(int which, int kind, double a, double b, const double * x);
 unsigned       a00_get_thetas(const a00_driver_t *, double * theta);
 /* current tau[] (2*species-1 entries); returns the number of populations */
 unsigned       a00_get_taus(const a00_driver_t *, double * tau);
