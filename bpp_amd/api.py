@@ -131,6 +131,8 @@ def lib():
         "bpa_plan_set_params_device": (i, [vp, i, vp]),
         "bpa_plan_work": (i, [vp, dp, dp, dp, C.POINTER(C.c_ulong), C.POINTER(C.c_ulong)]),
         "bpa_sampler_create": (vp, [vp, C.POINTER(vp), u, C.c_ulong]),
+        "bpa_sampler_options_from_env": (None, [C.POINTER(SamplerOptions)]),
+        "bpa_sampler_create_with": (vp, [vp, C.POINTER(vp), u, C.c_ulong, C.POINTER(SamplerOptions)]),
         "bpa_sampler_destroy": (None, [vp]),
         "bpa_sampler_set_tree": (i, [vp, u, C.POINTER(i), C.POINTER(i), dp, i]),
         "bpa_sampler_set_species_tree": (i, [vp, i, C.POINTER(i), dp, dp]),
@@ -208,7 +210,7 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_device_count", "bpa_engine_cre
             "bpa_p2p_create", "bpa_p2p_connect", "bpa_p2p_allreduce", "bpa_p2p_status", "bpa_p2p_destroy", "bpa_p2p_set_timeout", "bpa_plans_launch_exchange", "bpa_plans_launch",
             "bpa_plan_set_params", "bpa_plan_set_params_device", "bpa_engine_stage",
             "bpa_plan_work", "bpa_engine_enable_timing", "bpa_engine_timing", "bpa_engine_set_timing_stride", "bpa_engine_timing_work", "bpa_engine_timing_work_codes", "bpa_plan_work_codes",
-            "bpa_sampler_create", "bpa_sampler_destroy", "bpa_sampler_set_tree", "bpa_sampler_initialize",
+            "bpa_sampler_options_from_env", "bpa_sampler_create_with", "bpa_sampler_create", "bpa_sampler_destroy", "bpa_sampler_set_tree", "bpa_sampler_initialize",
             "bpa_sampler_set_species_tree", "bpa_sampler_set_tip_species", "bpa_sampler_set_finetune",
             "bpa_finetune_onestep", "bpa_sampler_adapt_finetune", "bpa_sampler_burnin", "bpa_burnin_schedule", "bpa_sweep_schedule", "bpa_exchange_layout",
             "bpa_sampler_set_tau_prior", "bpa_sampler_get_taus", "bpa_sampler_get_tree_msc",
@@ -586,14 +588,46 @@ def locus_root_loglikelihood(locus, root, persite=False):
     return locus.root_loglikelihood(root.clv_index, root.scaler_index, persite)
 
 
-class Sampler:
-    """device-resident per-locus proposal control (bpa_sampler_t)"""
+class SamplerOptions(C.Structure):
+    """bpa_sampler_options (bpp_amd.h)"""
+    _fields_ = [("size", C.c_uint), ("implementation", C.c_int), ("composite", C.c_int), ("chain", C.c_int),
+                ("host_decisions", C.c_int), ("debug", C.c_uint), ("launch_times", C.c_int), ("inject", C.c_long),
+                ("inject_wg0", C.c_int), ("diff", C.c_int), ("decision_log", C.c_int)]
 
-    def __init__(self, engine, loci, data, seed=1):
+    @classmethod
+    def from_env(cls):
+        o = cls()
+        lib().bpa_sampler_options_from_env(C.byref(o))
+        return o
+
+
+class Sampler:
+    """device-resident per-locus proposal control (bpa_sampler_t).  The keyword arguments are the fields of bpa_sampler_options
+    (bpp_amd.h); one left at None keeps what bpa_sampler_options_from_env reads from the environment:
+      implementation  "auto", "sweep" (one launch per step), "generic" or "big": which sampler takes loci that would fit another
+      composite       False: no composite for loci of several kinds
+      chain           the generic sampler's per-locus steps as one launch: False never, True whenever possible
+      host_decisions  True: the program's THETA / TAU / MIX of a generic sampler decided on the host
+      debug (bit mask), launch_times, inject (k, or (k, True): workgroup 0 alone), diff, decision_log: the diagnostics"""
+    IMPLEMENTATIONS = {"auto": -1, "sweep": 0, "generic": 1, "big": 4}
+
+    def __init__(self, engine, loci, data, seed=1, *, implementation=None, composite=None, chain=None, host_decisions=None,
+                 debug=None, launch_times=None, inject=None, diff=None, decision_log=None):
         L = lib()
         self.engine, self.n = engine, len(loci)
         self._arr = (C.c_void_p * self.n)(*[l.h for l in loci])
-        self.h = L.bpa_sampler_create(engine.h, self._arr, self.n, seed)
+        opt = SamplerOptions.from_env()
+        if implementation is not None:
+            if implementation not in self.IMPLEMENTATIONS:
+                raise BpaError(f"Sampler: implementation is one of {sorted(self.IMPLEMENTATIONS)}, not {implementation!r}")
+            opt.implementation = self.IMPLEMENTATIONS[implementation]
+        if inject is not None:
+            opt.inject, opt.inject_wg0 = (int(inject[0]), int(bool(inject[1]))) if isinstance(inject, tuple) else (int(inject), 0)
+        for name, v in (("composite", composite), ("chain", chain), ("host_decisions", host_decisions), ("debug", debug),
+                        ("launch_times", launch_times), ("diff", diff), ("decision_log", decision_log)):
+            if v is not None:
+                setattr(opt, name, int(v))
+        self.h = L.bpa_sampler_create_with(engine.h, self._arr, self.n, seed, C.byref(opt))
         if not self.h:
             raise BpaError(_err())
         ip = C.POINTER(C.c_int)
@@ -664,8 +698,8 @@ class Sampler:
     def set_prior_kinds(self, theta="gamma", tau="gamma"):
         """The families (alpha, beta) of set_theta_prior / set_tau_prior belong to: "gamma" (BPP's 'thetaprior = gamma a b',
         the default here) or "invgamma" (BPP's own default: 'thetaprior = invgamma a b e', 'tauprior = invgamma a b'); the
-        integers 0 / 1 are taken too.  Before initialize.  On the generic sampler (BPA_SMP_GENERIC=1 forces it), the big-tree
-        sampler and the one-launch-per-step sampler (BPA_SMP_V1=1), under both move sets; the persistent kernel, a composite
+        integers 0 / 1 are taken too.  Before initialize.  On the generic sampler (implementation="generic" forces it), the big-tree
+        sampler and the one-launch-per-step sampler (implementation="sweep"), under both move sets; the persistent kernel, a composite
         and a sampler that exchanges sums with other ranks have the gamma priors only and raise"""
         def kind(k):
             if isinstance(k, str):

@@ -157,35 +157,34 @@ static int run_all(bpa_composite * c, bpa_engine * e, std::function<int(bpa_samp
 }
 }  // namespace comp
 
-static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed);
-
-// the kinds the specialised samplers take; -1: none of them (the caller reports), 4: the big-tree sampler's
-static int comp_kind_of(const bpa_locus * l, bpa_engine * e)
+// THE statement of which sampler takes a locus (sampler_create_plain counts the kinds, comp_create deals the loci by them):
+// KIND_LDS the LDS kernels of sampler.hpp / sweep2.hpp, KIND_GEN_JC / KIND_GEN_KL the generic path's JC69 / multi-category
+// records, KIND_20 its 20-state form, KIND_BIG the big-tree sampler; below 0 none of them, by the refusal that reports it
+static int comp_kind_of(const bpa_locus * l, bpa_engine * e, const bpa_sampler_options & opt)
 {
   const bool counts = l && l->eng == e && l->alive && l->tips >= 2 && l->clv_buffers == 2*(l->tips - 1) && l->prob_matrices == 2*(2*l->tips - 2);
-  if (!counts) return -1;
-  if (l->states == 4 && (l->tips > (unsigned)gsm::NT || l->scale_buffers != 0 || l->dev.unphased_length)) return 4;
-  if (l->scale_buffers != 0 || l->dev.unphased_length) return -1;
-  if (l->states == 20) return (l->tips <= (unsigned)gsm::NT && l->rate_cats <= 4) ? 3 : -1;
-  if (l->states != 4) return -1;
+  if (!counts) return KIND_NONE;
+  // beyond 16 tips, with scalers, as an unphased diploid or when asked for, a 4-state locus takes the big-tree sampler (bigsampler.hpp)
+  if (l->states == 4 && (opt.implementation == BPA_SAMPLER_BIG || l->tips > (unsigned)gsm::NT || l->scale_buffers != 0 || l->dev.unphased_length))
+    return (l->tips <= (unsigned)gbig::BT && (l->scale_buffers == 0 || l->scale_buffers == 2*(l->tips - 1))) ? KIND_BIG : KIND_BIG_OVER;
+  if (l->scale_buffers != 0 || l->dev.unphased_length || (l->states != 4 && l->states != 20)) return KIND_NONE;
+  if (l->states == 20) return (l->tips <= (unsigned)gsm::NT && l->rate_cats <= 4) ? KIND_20 : KIND_20_OVER;
   const bool jc1 = l->rate_cats == 1 && l->dev.model == 0;
-  if (jc1 && l->tips <= (unsigned)smp::MAXTIPS && l->sites <= (unsigned)smp::BS && !smp_env_generic()) return 0;      // the LDS kernels
-  if (!(l->tips <= (unsigned)gsm::NT && l->rate_cats <= 8 && l->sites*l->rate_cats < PACK_BS)) return -1;
-  if (jc1) return 1;                                     // generic path, JC69 records
-  if (l->rate_cats > 1) return 2;                        // generic path, multi-category records
-  return -1;
+  if (jc1 && l->tips <= (unsigned)smp::MAXTIPS && l->sites <= (unsigned)smp::BS && opt.implementation != BPA_SAMPLER_GENERIC) return KIND_LDS;
+  if (!(l->tips <= (unsigned)gsm::NT && l->rate_cats <= 8 && l->sites*l->rate_cats < PACK_BS)) return KIND_4_OVER;
+  return jc1 ? KIND_GEN_JC : l->rate_cats > 1 ? KIND_GEN_KL : KIND_4_OVER;
 }
 
 // a composite where the loci are of more than one kind (and none wants the big-tree sampler); nullptr + *plain = true: not needed
-static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, bool * plain)
+static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, const bpa_sampler_options & opt, bool * plain)
 {
   *plain = true;
-  if (getenv("BPA_SMP_NO_COMPOSITE") || smp_env_big()) return nullptr;
+  if (!opt.composite) return nullptr;
   std::vector<unsigned> grp[4];
   for (unsigned i = 0; i < nloci; ++i)
   {
-    const int k = comp_kind_of(loci[i], e);
-    if (k < 0 || k == 4) return nullptr;                   // (the plain path reports, or takes the whole set as big trees)
+    const int k = comp_kind_of(loci[i], e, opt);
+    if (k < 0 || k == KIND_BIG) return nullptr;                   // (the plain path reports, or takes the whole set as big trees)
     grp[k].push_back(i);
   }
   // a handful of LDS-kernel loci next to generic JC69 loci: not worth a part of their own
@@ -195,7 +194,7 @@ static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, u
   if (kinds < 2) return nullptr;
   *plain = false;
   bpa_sampler * s = new bpa_sampler();
-  s->eng = e; s->nloci = nloci; s->seed = seed;
+  s->eng = e; s->nloci = nloci; s->seed = seed; s->opt = opt;
   s->loci.assign(loci, loci + nloci);
   bpa_composite * c = new bpa_composite();
   s->comp = c;
@@ -205,7 +204,7 @@ static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, u
     if (grp[k].empty()) continue;
     std::vector<bpa_locus_t *> sub;
     for (unsigned i : grp[k]) sub.push_back(loci[i]);
-    bpa_sampler * p = sampler_create_plain(e, sub.data(), (unsigned)sub.size(), seed);
+    bpa_sampler * p = sampler_create_plain(e, sub.data(), (unsigned)sub.size(), seed, opt);
     if (!p) { for (auto * q : c->parts) bpa_sampler_destroy(q); delete c; delete s; return nullptr; }
     p->stream_index = grp[k];
     for (unsigned j = 0; j < grp[k].size(); ++j)

@@ -601,7 +601,7 @@ __global__ void __launch_bounds__(1024) gsum_decide_kernel(const double * __rest
 // decision on the rates' mean — no likelihood work.  HOW = 0: the window (in (-1/2, 1/2)) and the acceptance number are the host's
 // (the uniform kernel: gs_decide's way); 1: both come from the global stream of the decisions taken on the device (GDecState::z:
 // BPP's generator, Bactrian-Laplace window, its acceptance rule) and the stream goes back there; 2: the sum only, the host decides
-// (BPA_GS_HOSTDEC) and brings the result with HOW = 3 (w: the new mean or 0 for a rejection)
+// (the options' host_decisions) and brings the result with HOW = 3 (w: the new mean or 0 for a rejection)
 template <int HOW>
 __global__ void __launch_bounds__(1024) gmubar_kernel(const double * __restrict__ mui, uint32_t T, GLrState * lr, uint32_t * zstate,
                                                       double ft_mubar, double a_mui, double a_mubar, double b_mubar, double w, double u)
@@ -737,7 +737,7 @@ __global__ void gprog_apply_kernel(const GApply a, uint32_t epoch, uint32_t * fl
 // step kernels read from GDecState instead of their arguments.  The global stream, the fits (k, T, a, b, c per population) and
 // the move-type counters live in GDecState between launches.  Stream order = a00_driver.c's = the host form's:
 // [first TAU's window] [THETA: choices + windows] [Gibbs variates] [acceptance numbers] [TAU: variates, acceptance] [next window] ...
-// The host form stays as the trajectory reference (BPA_GS_HOSTDEC=1) — same decisions, tests/test_gpu_gsampler.py.
+// The host form stays as the trajectory reference (the options' host_decisions) — same decisions, tests/test_gpu_gsampler.py.
 //
 // The sums arrive as DOUBLES in the all-reduce callback's format (gs_prog_allreduce): a likelihood / Jacobian sum as it is, a
 // non-negative 64-bit integer sum as two doubles holding its upper and lower 32 bits (exact for any number of ranks) — so several

@@ -11,7 +11,7 @@
 // proposal is gstep_kernel's, statement for statement: the previous step is settled first (its decision, or the roll-back
 // from the undo copy), the state a rejection comes back to is saved, the step is written as the records of the engine's
 // kernels (StepRec / StepOp / MatRec2, or the OpDev ranges of the 20-state kernels and of the chain below), the tree goes
-// back to HBM.  BPA_GS_DIFF=1 (gsampler_host.hpp) runs a step by both kernels from the same state and compares all of that.
+// back to HBM.  The options' diff (gsampler_host.hpp) runs a step by both kernels from the same state and compares all of that.
 // The other modes (settle + THETA statistics, start-up, the substitution-parameter moves) stay with gstep_kernel.
 // 12-14 us a launch for <= 8 tips, 15-20 for <= 16 (profiles/r4/gstep2.txt): one wave's ~9 500 instructions.
 #pragma once

@@ -336,7 +336,7 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   const bool touches_eigen = mode == 6 || mode == 7 || (s->g_pend == 4 && (s->g_pend_mode == 6 || s->g_pend_mode == 7));
   a.fuse_eigen = (touches_eigen && mode >= 4 && mode != 10 && !s->g_s20 && !s->g_alljc && e->usedata && !s->g_eigen_dirty) ? 1u : 0u;
   if (touches_eigen && !a.fuse_eigen) s->g_eigen_dirty = true;
-  // diagnostics (BPA_GS_DIFF=1): a GAGE / GSPR step by both kernels from the same state, whatever differs is reported;
+  // diagnostics (the options' diff): a GAGE / GSPR step by both kernels from the same state, whatever differs is reported;
   // the run goes on with the one-lane kernel's result
 #define GS2_CASES(NT_, BPP_, GRID_, ST_) switch (a.mode) { \
       case 0: hipLaunchKernelGGL((gsm2::gstep2_kernel<0, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; case 1: hipLaunchKernelGGL((gsm2::gstep2_kernel<1, NT_, BPP_>), GRID_, dim3(64), 0, ST_, a); break; \
@@ -350,13 +350,13 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
                                            case 2: hipLaunchKernelGGL((gsm::gstep_kernel<2, 8>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; default: hipLaunchKernelGGL((gsm::gstep_kernel<3, 8>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; } \
     else switch (a.mode) { case 0: hipLaunchKernelGGL((gsm::gstep_kernel<0, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; case 1: hipLaunchKernelGGL((gsm::gstep_kernel<1, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; \
                            case 2: hipLaunchKernelGGL((gsm::gstep_kernel<2, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; default: hipLaunchKernelGGL((gsm::gstep_kernel<3, 16>), GRID_, dim3(gsm::GBS), 0, ST_, a); break; } } while (0)
-  static const bool gs_diff = getenv("BPA_GS_DIFF") != nullptr;
+  const bool gs_diff = s->opt.diff != 0;
   // the step's P-matrices by the proposal's lane groups (gstep2_body) instead of a launch of their own: 4-state loci on the
   // packing, no substitution-parameter step pending or rolled back since the eigensystems were last refreshed.  A pending RATE step (mode 9) does not turn
   // this off: it wrote no parameter block, and the lane group reads the locus's rate after it has settled that step
   s->g_pm_fused = mode <= 3 && !gs_diff && !s->g_s20 && !s->g_alljc && e->usedata && (s->g_pend != 4 || s->g_pend_mode == 9) && !s->g_eigen_dirty;
   a.fuse_pm = s->g_pm_fused ? 1u : 0u;
-  if (s->kernel_bpp && mode <= 3 && gs_diff) return fail("bpa_sampler: BPP's proposal kernel has no one-lane form (BPA_GS_DIFF is the uniform kernel's diagnostic)");
+  if (s->kernel_bpp && mode <= 3 && gs_diff) return fail("bpa_sampler: BPP's proposal kernel has no one-lane form (the options' diff, BPA_GS_DIFF, is the uniform kernel's diagnostic)");
   if (gs_diff && mode <= 3 && !s->g_forked)
   {
     const unsigned n = s->nloci;
@@ -644,14 +644,14 @@ static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci ste
   return 1;
 }
 
-// GAGE + GSPR of every locus in one launch (gsampler2.hpp: gchain_kernel).  BPA_GS_CHAIN=0 / 1: never / whenever possible.
+// GAGE + GSPR of every locus in one launch (gsampler2.hpp: gchain_kernel).  The options' chain = 0 / 1: never / whenever possible.
 // Default: small JC69 sets only — up to 1 024 loci of at most 64 patterns on average (config 5: 913 -> 1 096 it/s).  With
 // several rate categories or hundreds of patterns a wave per locus walking one pattern per lane loses to the packing's
 // kernels even when those are launch-bound (config 3's share of 1 250 loci: 516 it/s by launches, 337 chained).
 static bool gs_chain_wanted(const bpa_sampler * s)
 {
   if (s->g_s20 || !s->eng->usedata || s->maxtips < 2) return false;
-  if (s->env_chain >= 0) return s->env_chain != 0;
+  if (s->opt.chain >= 0) return s->opt.chain != 0;
   return s->g_alljc && s->nloci <= 1024u && s->g_npat <= 64u*s->nloci;
 }
 static int gs_chain(bpa_sampler * s)
@@ -731,18 +731,17 @@ static int gs_initialize(bpa_sampler * s)
 // theta_step_gibbs / tau_step / mix_step of csrc/host/a00_driver.c, statement for statement on the host side (same global
 // stream, same order of draws: [first TAU's window] [THETA: choices + windows] [Gibbs variates] [acceptance numbers] [TAU:
 // variates, acceptance] [next window] ...), the loci's part — proposal, likelihood, the sums — on the device.
-static void gs_declog(const char * what, int k, double lnacc, int acc)
+static void gs_declog(const bpa_sampler * s, const char * what, int k, double lnacc, int acc)
 {
-  static const bool on = getenv("A00_DECLOG") != nullptr;          // (the host driver's switch: the two logs line up)
-  if (on) fprintf(stderr, "[gsp] %s %d lnacc %.17g u -1 -> %d\n", what, k, lnacc, acc);
+  if (s->opt.decision_log) fprintf(stderr, "[gsp] %s %d lnacc %.17g u -1 -> %d\n", what, k, lnacc, acc);
 }
 
-// the decisions on the device (gdec_kernel, gsampler.hpp) unless BPA_GS_HOSTDEC=1 (the host form below: the trajectory
+// the decisions on the device (gdec_kernel, gsampler.hpp) unless the options say host_decisions (the host form below: the trajectory
 // reference).  Several ranks: the sums — doubles in the callback's own format — go through the all-reduce callback ON THE STREAM
 // between the sum kernel and gdec_kernel (gs_dev_allreduce): with a stream-ordered collective (RCCL) no host waits for anything
 static bool gs_prog_dev_wanted(const bpa_sampler * s)
 {
-  return s->big || !s->env_hostdec;           // (the big-tree sampler has the device form only)
+  return s->big || !s->opt.host_decisions;           // (the big-tree sampler has the device form only)
 }
 
 // the device's counters by move type and its copy of the global stream come back to the host's (adapt_finetune, a download)
@@ -926,7 +925,7 @@ static int gs_prog_theta(bpa_sampler * s)
               + a00_theta_gibbs_hastings(fa[p], fb[p], s->gp_theta[p], tnew[p]);
       acc = lnacc == lnacc && tnew[p] > 0 && (lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc));
     }
-    gs_declog(slide[p] ? "theta" : "thetag", p, lnacc, acc);
+    gs_declog(s, slide[p] ? "theta" : "thetag", p, lnacc, acc);
     if (slide[p]) { s->gp_pj[8]++; s->gp_pj[9] += acc ? 1u : 0u; }
     if (acc) { a.nacc++; s->gp_theta[p] = tnew[p]; a.theta_mask |= 1u << p; a.theta[p] = tnew[p]; if (!slide[p]) a.ngacc++; }
     if (!slide[p]) a.ngprop++;
@@ -995,7 +994,7 @@ static int gs_prog_tau(bpa_sampler * s, int q)
     s->gp_theta[p] = tn;
   }
   const bool acc = sum >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(sum);
-  gs_declog("tau", q, sum, acc);
+  gs_declog(s, "tau", q, sum, acc);
   s->gp_pj[4]++; s->gp_pj[5] += acc ? 1u : 0u;
   s->grng = (a00_rng_t)gz;
   if (acc)
@@ -1052,7 +1051,7 @@ static int gs_prog_mix(bpa_sampler * s)
     lnacc += a00_mix_tau_prior_lnratio(smp::tau_kind(s->sp), s->sp.tau_alpha, s->sp.tau_beta, s->sp.S, lnc, s->gp_tau[root], s->gp_tau[root]*c);
   lnacc += lnacc_theta;
   const bool acc = lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc);
-  gs_declog("mix", 0, lnacc, acc);
+  gs_declog(s, "mix", 0, lnacc, acc);
   s->gp_pj[6]++; s->gp_pj[7] += acc ? 1u : 0u;
   s->grng = (a00_rng_t)gz;
   gsm::GApply a{};
@@ -1133,7 +1132,7 @@ static int gs_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
 // MUBAR: the pending rate step is settled first (a launch of its own: the sum must see the rates the loci kept), then ONE
 // launch sums and decides — with the host's two numbers (our own kernel), from the device's global stream (the program's moves
 // decided on the device: the two draws sit between MIX's acceptance number and the next iteration's first window, where
-// a00_iterate puts them) — or, BPA_GS_HOSTDEC=1, the host fetches the sum and decides, as that form does for TAU and MIX
+// a00_iterate puts them) — or, host_decisions, the host fetches the sum and decides, as that form does for TAU and MIX
 static int gs_mubar(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
@@ -1159,7 +1158,7 @@ static int gs_mubar(bpa_sampler * s)
     const double m_new = std::exp(l_new);
     const double lnacc = A00_MUBAR_LNACC(l_old, l_new, st.mubar, m_new, am/st.mubar, am/m_new, am, a, b, (double)s->nloci, st.sum);
     const bool acc = lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc);
-    gs_declog("mubar", 0, lnacc, acc);
+    gs_declog(s, "mubar", 0, lnacc, acc);
     s->grng = (a00_rng_t)gz;
     hipLaunchKernelGGL((gsm::gmubar_kernel<3>), dim3(1), dim3(1), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, acc ? m_new : 0.0, 0.0);
   }
@@ -1355,7 +1354,7 @@ static int lr_refuse(const bpa_sampler * s, const char * who)
   if (!s->comp && (s->generic || s->big)) return 1;
   static thread_local std::string msg;
   msg = std::string(who) + ": per-locus rates and their moves run on the generic and the big-tree sampler only (this one is the " + kind +
-        " sampler); BPA_SMP_GENERIC=1 makes the generic sampler take loci the LDS kernels would otherwise";
+        " sampler); implementation = BPA_SAMPLER_GENERIC in the options at creation (from the environment: BPA_SMP_GENERIC=1) makes the generic sampler take loci the LDS kernels would otherwise";
   return fail(msg.c_str());
 }
 
@@ -1423,7 +1422,7 @@ static int hered_refuse(const bpa_sampler * s, const char * who)
   if (!s->comp && (s->generic || s->big)) return 1;
   static thread_local std::string msg;
   msg = std::string(who) + ": heredity scalars and their move run on the generic and the big-tree sampler only (this one is the " + kind +
-        " sampler); BPA_SMP_GENERIC=1 makes the generic sampler take loci the LDS kernels would otherwise";
+        " sampler); implementation = BPA_SAMPLER_GENERIC in the options at creation (from the environment: BPA_SMP_GENERIC=1) makes the generic sampler take loci the LDS kernels would otherwise";
   return fail(msg.c_str());
 }
 

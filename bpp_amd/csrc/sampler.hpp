@@ -1096,10 +1096,28 @@ __global__ void __launch_bounds__(1024) theta_sum_decide_kernel(const int8_t * _
 #include "bigsampler.hpp"
 
 // ------------------------------------------------------------------------------------ host ---
-// which device sampler takes the loci, when a test wants another than the one that fits (read when a sampler is made, not cached:
-// a test process makes samplers of several kinds)
-static bool smp_env_generic() { return getenv("BPA_SMP_GENERIC") != nullptr; }
-static bool smp_env_big() { return getenv("BPA_SMP_BIG") != nullptr; }
+// what a sampler is told at creation besides its loci (bpp_amd.h); the environment is read HERE and nowhere else in the sampler
+// code, when bpa_sampler_create asks for it: a process makes samplers of several kinds, nothing on a launch path reads it
+static bpa_sampler_options sampler_default_options()
+{
+  bpa_sampler_options o{};
+  o.size = (unsigned)sizeof o; o.implementation = BPA_SAMPLER_AUTO; o.composite = 1; o.chain = -1;
+  return o;
+}
+extern "C" void bpa_sampler_options_from_env(bpa_sampler_options * o)
+{
+  if (!o) return;
+  *o = sampler_default_options();
+  o->implementation = getenv("BPA_SMP_BIG") ? BPA_SAMPLER_BIG : getenv("BPA_SMP_GENERIC") ? BPA_SAMPLER_GENERIC : getenv("BPA_SMP_V1") ? BPA_SAMPLER_SWEEP : BPA_SAMPLER_AUTO;
+  o->composite = getenv("BPA_SMP_NO_COMPOSITE") == nullptr;
+  if (const char * v = getenv("BPA_GS_CHAIN")) o->chain = v[0] != '0';
+  o->host_decisions = getenv("BPA_GS_HOSTDEC") != nullptr;
+  if (const char * dv = getenv("BPA_SMP_DBG")) o->debug = (unsigned)atoi(dv);
+  o->launch_times = getenv("BPA_SMP_TRACE") != nullptr;
+  if (const char * inj = getenv("BPA_SMP_INJECT")) { o->inject = atol(inj); o->inject_wg0 = strstr(inj, ",w") != nullptr; }
+  o->diff = getenv("BPA_GS_DIFF") != nullptr;
+  o->decision_log = getenv("A00_DECLOG") != nullptr;          // (the host driver's switch: the two logs line up)
+}
 
 struct bpa_sampler
 {
@@ -1215,12 +1233,10 @@ struct bpa_sampler
   unsigned long g_evals = 0;            // launches of the likelihood step kernel (bpa_sampler_work reports them as `sweeps`)
   unsigned nblocks = 0, epoch = 0;
   bool logpr_stale = false;     // thetas moved since the trees' densities were stored (Args::refresh_logpr)
-  // diagnostic switches, read once at creation: BPA_SMP_DBG (bit mask, see Args::dbg), BPA_SMP_TRACE (per-launch times on stderr)
-  uint32_t env_dbg = 0; bool env_trace = false;
-  // the generic sampler's kept paths (read ONCE, at creation: nothing reads the environment on the launch path, and a test can
-  // still make samplers of either kind in one process)
-  bool env_hostdec = false; int env_chain = -1;
-  long env_inject = 0; uint32_t env_inject_bit = 1024u; long v2_launch_no = 0;    // BPA_SMP_INJECT=k[,w]: the k-th persistent launch with all-loci steps gives up at its first wait (w: workgroup 0 alone) — tests of the run-again path
+  // the options it was created with (bpp_amd.h: the forced implementation, the generic sampler's kept paths, the diagnostics);
+  // a part of a composite holds its parent's
+  bpa_sampler_options opt = sampler_default_options();
+  long v2_launch_no = 0;                // persistent launches with all-loci steps so far (opt.inject: the one that gives up at its first wait — tests of the run-again path)
   bool mix_pending = false;             // a mixing decision taken on the device has not been applied yet
   a00_rng_t grng = 0;
   unsigned long seed = 0, launches = 0, sweeps = 0;
@@ -1229,7 +1245,7 @@ struct bpa_sampler
   uint32_t h_counters[4] = {0, 0, 0, 0};   // all-loci proposals / accepted (+ of those: THETA Gibbs draws / accepted) at the last invalidation (re-uploaded)
   bool host_current = false;            // the host copies (h_trees / g_trees, g_sm_host) hold the device's state: set by a download, cleared by iterate
   // ---- the persistent iteration kernel (sweep2.hpp): one GPU, loci that fit the sweep kernel, root = the last node
-  bool v2_ok = false, env_v1 = false;
+  bool v2_ok = false;
   int v2_nt = 0;                        // its instance: 4 or 8 tips
   int v2_retries = 0;                   // persistent launches that timed out in a row (sampler_download runs their iterations again)
   bool v2_prog = false;                 // ... with the program's moves: wave 0 of every workgroup is the control wave (no loci)
@@ -1253,7 +1269,7 @@ struct bpa_sampler
   bpa_p2p * p2p = nullptr;              // several GPUs, the sums exchanged INSIDE the persistent kernel over xGMI mailboxes (bpa_sampler_set_p2p)
   unsigned long v2_iters = 0;           // iterations run by persistent launches (bpa_sampler_timing)
   // ---- the sample trace (bpa_sampler_set_trace: rows of tau, theta and lnL every rowlog_every iterations; nothing to do with the
-  // BPA_SMP_TRACE diagnostic, env_trace).  rowlog_it: iterations of bpa_sampler_iterate counted since set_trace (not while
+  // launch_times diagnostic of the options).  rowlog_it: iterations of bpa_sampler_iterate counted since set_trace (not while
   // rowlog_hold: burn-in); the device holds rowlog_rows [rowlog_cap][width] and the count of all rows ever written, rowlog_n;
   // rowlog_base of them have been moved to rowlog_store (the host-side store, oldest first from rowlog_head on); rowlog_enq:
   // row launches since the device buffer was last emptied (an upper bound of the rows in it)
@@ -1272,7 +1288,7 @@ static int rowlog_emit(bpa_sampler * s, const void * lnl0, size_t stride, const 
 // the iterations up to the next row (the persistent launches end there)
 static unsigned rowlog_until_row(const bpa_sampler * s) { return s->rowlog_every - (unsigned)(s->rowlog_it % s->rowlog_every); }
 
-static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, bool * plain);
+static bpa_sampler * comp_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, const bpa_sampler_options & opt, bool * plain);
 static void comp_destroy(bpa_sampler * s);
 static int comp_invalidate(bpa_sampler * s);
 static int comp_upload(bpa_sampler * s);
@@ -1287,78 +1303,76 @@ static long comp_trace_read(bpa_sampler * s, double * rows, unsigned long max_ro
 template <class F> static int comp_each(bpa_sampler * s, F f);
 #define COMP_FAIL(msg) do { if (s->comp) return fail(msg); } while (0)
 
-static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed);
-extern "C" bpa_sampler_t * bpa_sampler_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci,
-                                              unsigned long seed)
+// which sampler a locus fits (comp_kind_of, composite.hpp); below 0: none, and which refusal says so
+enum { KIND_LDS = 0, KIND_GEN_JC = 1, KIND_GEN_KL = 2, KIND_20 = 3, KIND_BIG = 4, KIND_NONE = -1, KIND_BIG_OVER = -2, KIND_20_OVER = -3, KIND_4_OVER = -4 };
+static int comp_kind_of(const bpa_locus * l, bpa_engine * e, const bpa_sampler_options & opt);
+static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, const bpa_sampler_options & opt);
+extern "C" bpa_sampler_t * bpa_sampler_create_with(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci,
+                                                   unsigned long seed, const bpa_sampler_options * given)
 {
-  if (!e || !loci || !nloci) { fail("bpa_sampler_create: null argument"); return nullptr; }
+  if (!e || !loci || !nloci || !given) { fail("bpa_sampler_create: null argument"); return nullptr; }
+  // (a caller compiled against a shorter struct: the defaults for what it does not know of)
+  bpa_sampler_options opt = sampler_default_options();
+  if (given->size < sizeof(unsigned)) { fail("bpa_sampler_create_with: options without their size (bpa_sampler_options_from_env sets it)"); return nullptr; }
+  std::memcpy(&opt, given, std::min((size_t)given->size, sizeof opt));
+  opt.size = (unsigned)sizeof opt;
   std::lock_guard<std::recursive_mutex> lock_(e->mtx);
   // loci of more than one kind: a part per kind, stepped together (composite.hpp)
   bool plain = true;
-  bpa_sampler * c = comp_create(e, loci, nloci, seed, &plain);
+  bpa_sampler * c = comp_create(e, loci, nloci, seed, opt, &plain);
   if (c || !plain) return c;
-  return sampler_create_plain(e, loci, nloci, seed);
+  return sampler_create_plain(e, loci, nloci, seed, opt);
+}
+extern "C" bpa_sampler_t * bpa_sampler_create(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci,
+                                              unsigned long seed)
+{
+  bpa_sampler_options opt;
+  bpa_sampler_options_from_env(&opt);
+  return bpa_sampler_create_with(e, loci, nloci, seed, &opt);
 }
 
-static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed)
+static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const * loci, unsigned nloci, unsigned long seed, const bpa_sampler_options & opt)
 {
   bpa_sampler * s = new bpa_sampler();
-  s->eng = e; s->nloci = nloci; s->seed = seed; s->grng = a00_rng_seed(seed, A00_GLOBAL_STREAM);
+  s->eng = e; s->nloci = nloci; s->seed = seed; s->grng = a00_rng_seed(seed, A00_GLOBAL_STREAM); s->opt = opt;
   s->sp.theta_slide_prob = 0.1;
   s->loci.assign(loci, loci + nloci);
-  // the LDS sweep kernel (JC69, one rate category, <= 8 tips, <= 64 patterns) where every locus fits it, else the generic
-  // path over the engine's step kernels (any 4-state model on the engine's packing, <= 16 tips; BPA_SMP_GENERIC=1 forces it)
-  bool fits_sweep = !smp_env_generic(), fits_generic = true, all_jc = true, all_kl = true;
-  unsigned n20 = 0, nbig = 0;
-  const bool force_big = smp_env_big();
+  // every locus's kind (comp_kind_of, composite.hpp: the one statement of what each sampler takes): the LDS sweep kernel where
+  // every locus fits it, else the generic path over the engine's step kernels, or the big-tree sampler
+  unsigned n[5] = {0, 0, 0, 0, 0}, over20 = 0, over4 = 0;
   for (unsigned i = 0; i < nloci; ++i)
   {
-    const bpa_locus * l = loci[i];
-    const bool counts = l && l->eng == e && l->alive && l->tips >= 2 && l->clv_buffers == 2*(l->tips - 1) && l->prob_matrices == 2*(2*l->tips - 2);
-    // beyond 16 tips, with scalers or as an unphased diploid a 4-state locus takes the big-tree sampler (bigsampler.hpp)
-    const bool wants_big = counts && l->states == 4 && (force_big || l->tips > (unsigned)gsm::NT || l->scale_buffers != 0 || l->dev.unphased_length);
-    if (wants_big)
+    const int k = comp_kind_of(loci[i], e, opt);
+    if (k == KIND_BIG_OVER)
     {
-      if (l->tips > (unsigned)gbig::BT || (l->scale_buffers != 0 && l->scale_buffers != 2*(l->tips - 1)))
-      {
-        fail("bpa_sampler_create: a locus of the big-tree sampler has <= 64 tips and no or 2 (tips - 1) scale buffers (method.c:4110-4146)");
-        delete s; return nullptr;
-      }
-      ++nbig; s->maxtips = std::max(s->maxtips, l->tips); s->g_rmax = std::max(s->g_rmax, l->rate_cats);
-      continue;
+      fail("bpa_sampler_create: a locus of the big-tree sampler has <= 64 tips and no or 2 (tips - 1) scale buffers (method.c:4110-4146)");
+      delete s; return nullptr;
     }
-    const bool base = counts && (l->states == 4 || l->states == 20) && l->scale_buffers == 0 && !l->dev.unphased_length;
-    if (!base)
+    if (k == KIND_NONE)
     {
       fail("bpa_sampler_create: loci must be 4- or 20-state (20-state: without scalers, not diploid), with the buffer counts of method.c:4110-4146");
       delete s; return nullptr;
     }
-    if (l->states == 20) { ++n20; fits_sweep = false; fits_generic = fits_generic && l->tips <= (unsigned)gsm::NT && l->rate_cats <= 4; all_jc = false;
-                           s->maxtips = std::max(s->maxtips, l->tips); s->g_rmax = std::max(s->g_rmax, l->rate_cats); continue; }
-    fits_sweep = fits_sweep && l->rate_cats == 1 && l->dev.model == 0 && l->tips <= (unsigned)smp::MAXTIPS && l->sites <= (unsigned)smp::BS;
-    fits_generic = fits_generic && l->tips <= (unsigned)gsm::NT && l->rate_cats <= 8 && l->sites*l->rate_cats < PACK_BS;
-    all_jc = all_jc && l->rate_cats == 1 && l->dev.model == 0;
-    all_kl = all_kl && l->rate_cats > 1;
-    s->maxtips = std::max(s->maxtips, l->tips);
-    s->g_rmax = std::max(s->g_rmax, l->rate_cats);
+    if (k >= 0) ++n[k]; else ++(k == KIND_20_OVER ? over20 : over4);
+    s->maxtips = std::max(s->maxtips, loci[i]->tips); s->g_rmax = std::max(s->g_rmax, loci[i]->rate_cats);
   }
-  if (nbig)
+  if (n[KIND_BIG])
   {
     // one big locus makes the whole sampler the big-tree one (its kernels take any 4-state locus)
+    bpa_sampler_options as_big = opt; as_big.implementation = BPA_SAMPLER_BIG;
     for (unsigned i = 0; i < nloci; ++i)
-      if (loci[i]->states != 4 || loci[i]->tips > (unsigned)gbig::BT || (loci[i]->scale_buffers != 0 && loci[i]->scale_buffers != 2*(loci[i]->tips - 1)))
+      if (comp_kind_of(loci[i], e, as_big) != KIND_BIG)
       {
         fail("bpa_sampler_create: the loci of a big-tree sampler are all 4-state with <= 64 tips");
         delete s; return nullptr;
       }
-    for (unsigned i = 0; i < nloci; ++i) { s->maxtips = std::max(s->maxtips, loci[i]->tips); s->g_rmax = std::max(s->g_rmax, loci[i]->rate_cats); }
     s->big = true;
     s->b_trees.assign(nloci, gbig::BTree{});
   }
-  else if (n20)
+  else if (n[KIND_20] || over20)
   {
     // amino-acid loci: the generic sampler's proposal control, the likelihood by the tiled 20-state kernels
-    if (n20 != nloci || !fits_generic)
+    if (n[KIND_20] != nloci)
     {
       fail("bpa_sampler_create: 20-state loci go together (no 4-state locus in the same sampler), with <= 16 tips and <= 4 rate categories");
       delete s; return nullptr;
@@ -1366,9 +1380,10 @@ static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const 
     s->generic = true; s->g_alljc = false; s->g_s20 = true;
     s->g_trees.assign(nloci, gsm::GTree{});
   }
-  else if (!fits_sweep)
+  else if (n[KIND_LDS] != nloci)
   {
-    if (!fits_generic || !(all_jc || all_kl))
+    const bool all_jc = n[KIND_LDS] + n[KIND_GEN_JC] == nloci, all_kl = n[KIND_GEN_KL] == nloci;
+    if (over4 || !(all_jc || all_kl))
     {
       fail("bpa_sampler_create: beyond the sweep kernel (JC69, 1 rate category, <= 8 tips, <= 64 patterns) the loci must all be JC69 with "
            "one rate category or all have several categories, with <= 16 tips and < 256 patterns x categories");
@@ -1378,12 +1393,6 @@ static bpa_sampler * sampler_create_plain(bpa_engine_t * e, bpa_locus_t * const 
     s->g_trees.assign(nloci, gsm::GTree{});
   }
   s->h_trees.assign(nloci, smp::Tree{});
-  if (const char * dv = getenv("BPA_SMP_DBG")) s->env_dbg = (uint32_t)atoi(dv);
-  s->env_trace = getenv("BPA_SMP_TRACE") != nullptr;
-  if (const char * inj = getenv("BPA_SMP_INJECT")) { s->env_inject = atol(inj); s->env_inject_bit = strstr(inj, ",w") ? 2048u : 1024u; }
-  { const char * v = getenv("BPA_GS_CHAIN"); s->env_chain = v ? (v[0] != '0' ? 1 : 0) : -1; }
-  s->env_hostdec = getenv("BPA_GS_HOSTDEC") != nullptr;
-  s->env_v1 = getenv("BPA_SMP_V1") != nullptr;
   s->sp.ft_gage = 0.004; s->sp.ft_gspr = 0.004; s->sp.ft_tau = 0.001; s->sp.ft_mix = 0.3;      // a00_create's defaults
   return s;
 }
@@ -1505,8 +1514,8 @@ extern "C" int bpa_sampler_set_prior_kinds(bpa_sampler_t * s, int theta_kind, in
   if (s->uploaded || s->started) return fail("bpa_sampler_set_prior_kinds: before bpa_sampler_initialize (as a00_set_prior_kinds)");
   if (s->allreduce || s->p2p) return fail("bpa_sampler_set_prior_kinds: several ranks have the gamma priors only (an all-reduce callback or the mailboxes are installed: run the loci on one rank)");
   // (which kernel runs the loci is settled at upload; loci that fit the persistent kernel get it unless one of these holds)
-  if (!(s->generic || s->big || s->env_v1 || s->env_trace))
-    return fail("bpa_sampler_set_prior_kinds: the persistent kernel has the gamma priors only: BPA_SMP_GENERIC=1 or BPA_SMP_V1=1 at creation");
+  if (!(s->generic || s->big || s->opt.implementation == BPA_SAMPLER_SWEEP || s->opt.launch_times))
+    return fail("bpa_sampler_set_prior_kinds: the persistent kernel has the gamma priors only: implementation = BPA_SAMPLER_GENERIC or BPA_SAMPLER_SWEEP in the options at creation (from the environment: BPA_SMP_GENERIC=1, BPA_SMP_V1=1)");
   s->sp.prior_kinds = (theta_kind == BPA_PRIOR_INVGAMMA ? 1 : 0) | (tau_kind == BPA_PRIOR_INVGAMMA ? 2 : 0);
   return 1;
 }
@@ -1716,11 +1725,11 @@ static bool v2_wants_prog(const bpa_sampler * s)
 }
 // v2_ok stays false where the kernel does not apply (the one-launch-per-step path of this file then runs): more loci than
 // stay resident on the device at once, a tree whose root is not its last node or whose buffer indices are not the
-// reference's start values toggled (gtree.c:2398, 2433: clv_index = pmatrix_index = node index), BPA_SMP_V1=1
+// reference's start values toggled (gtree.c:2398, 2433: clv_index = pmatrix_index = node index), implementation = BPA_SAMPLER_SWEEP
 static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & task_rec)
 {
   s->v2_ok = false;
-  if (s->env_v1 || s->generic || s->big) return 1;
+  if (s->opt.implementation == BPA_SAMPLER_SWEEP || s->generic || s->big) return 1;
   const unsigned T = s->nloci;
   const int npop = s->sp.npop;
   if (s->maxtips > 8 || npop > 15) return 1;
@@ -1774,7 +1783,7 @@ static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & 
   unsigned LWAVES = (LMAX > 4u && nwaves <= 4u*ncu) ? 4u : (prog && NT == 4 && LMAX >= 5u && nwaves <= 5u*ncu) ? 5u : LMAX;
   // BPA_SMP_DBG & 4096: deal densely — as few workgroups as hold the waves, evenly filled (LMAX or fewer waves: one workgroup
   // of all of them), so that a few dozen loci run in pairs and hand sets over
-  if (s->env_dbg & 4096u) { const unsigned g = (nwaves + LMAX - 1)/LMAX; LWAVES = std::max((nwaves + g - 1)/std::max(g, 1u), 1u); }
+  if (s->opt.debug & 4096u) { const unsigned g = (nwaves + LMAX - 1)/LMAX; LWAVES = std::max((nwaves + g - 1)/std::max(g, 1u), 1u); }
   const unsigned nwg = (nwaves + LWAVES - 1)/LWAVES;
   // every workgroup must be resident (they wait for each other's sums): one per CU — a workgroup takes most of a CU's LDS
   // sets change waves where a schedule is measured to win: the program's moves, four tips, 5 waves of loci — a chain of three
@@ -1785,8 +1794,8 @@ static int sampler_upload_v2(bpa_sampler * s, const std::vector<smp::TaskRec> & 
   // the two step costs in thousands of cycles, as NOTES §17 measured them: a wave served first, the younger wave of a pair while the older runs
   constexpr double SWEEP_STEP_ALONE = 11.9, SWEEP_STEP_YOUNG = 18.1;
   bool sched_on = false;
-  if (prog && NT == 4 && LWAVES == 5 && !(s->env_dbg & 8192u) && nprop_sweep <= 255u)
-    sched_on = bpa_sweep_schedule(LWAVES, nprop_sweep, SWEEP_STEP_ALONE, SWEEP_STEP_YOUNG, ((s->env_dbg >> 14) & 3u) ? (s->env_dbg >> 14) & 3u : 3u, reinterpret_cast<unsigned char *>(&sched)) > 1;
+  if (prog && NT == 4 && LWAVES == 5 && !(s->opt.debug & 8192u) && nprop_sweep <= 255u)
+    sched_on = bpa_sweep_schedule(LWAVES, nprop_sweep, SWEEP_STEP_ALONE, SWEEP_STEP_YOUNG, ((s->opt.debug >> 14) & 3u) ? (s->opt.debug >> 14) & 3u : 3u, reinterpret_cast<unsigned char *>(&sched)) > 1;
   const size_t base = sched_on ? v2_lds_handover<4>(LWAVES) : NT == 4 ? v2_lds_base<4>(prog) : v2_lds_base<8>(prog);
   const size_t lds_max = std::min<size_t>((size_t)prop.sharedMemPerBlock > 65536 ? (size_t)prop.sharedMemPerBlock : 160*1024, 160*1024) - 256;
   if (base > lds_max) return 1;
@@ -1950,13 +1959,13 @@ static int sampler_launch(bpa_sampler * s, unsigned mode, double mix_c, double m
   a.bfbeta = e->usedata ? e->bfbeta : 0.0;
   a.refresh_logpr = s->logpr_stale ? 1u : 0u; s->logpr_stale = false;
   a.pop_nc = s->pop_nc.p; a.pop_t2h = s->pop_t2h.p; a.lograt = s->lograt.p; a.ntasks = s->nloci; a.part_out = s->wg_part;
-  a.dbg = s->env_dbg;
+  a.dbg = s->opt.debug;
   a.taus = s->taus.p; a.tau_q = tau_q; a.tau_u = tau_u; a.sp = s->sp; a.mix_lnc = mix_lnc;
   a.nsteps_gage = s->maxtips - 1; a.nsteps_gspr = 2*s->maxtips - 2; a.mix_c = mix_c;
   // the unrolled node passes of the leader's code are sized by the largest tree: 4-tip loci get their own instance
   void (*kern)(const smp::Args) = s->maxtips <= 4 ? smp::sweep_kernel<4> : smp::sweep_kernel<smp::MAXTIPS>;
   const size_t lds = (size_t)2*(s->maxtips - 1)*smp::BS*4*sizeof(double);
-  if (s->env_trace)
+  if (s->opt.launch_times)
   {
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     hipExtLaunchKernelGGL(kern, dim3(s->nblocks), dim3(smp::BS), lds, e->stream, e0, e1, 0, a);
@@ -2492,12 +2501,12 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
     a.sched = s->v2_sched.p; a.sched_on = s->v2_sched_on ? 1u : 0u;
     // the exchange's layout; BPA_SMP_DBG bits 16-18: 1 .. 4 = 8, 16, 32, 64 shards a set (anything else: the default)
     {
-      const unsigned cs = (s->env_dbg >> 16) & 7u;
+      const unsigned cs = (s->opt.debug >> 16) & 7u;
       a.xshards = cs >= 1u && cs <= 4u ? 4u << cs : XSHARDS_DEFAULT;
     }
     a.nsteps_gage = s->maxtips - 1; a.nsteps_gspr = 2*s->maxtips - 2;
-    a.theta_mask = theta_mask; a.do_allloci = allloci ? 1u : 0u; a.dbg = s->env_dbg;
-    if (allloci && ++s->v2_launch_no == s->env_inject) a.dbg |= s->env_inject_bit;
+    a.theta_mask = theta_mask; a.do_allloci = allloci ? 1u : 0u; a.dbg = s->opt.debug;
+    if (allloci && ++s->v2_launch_no == s->opt.inject) a.dbg |= s->opt.inject_wg0 ? 2048u : 1024u;
     if (s->p2p && allloci)
     {
       a.peers = s->p2p->d_peer.p; a.mail = s->p2p->mail; a.rank = s->p2p->rank; a.world = s->p2p->world; a.slot_bytes = s->p2p->slot_bytes;
@@ -2511,7 +2520,7 @@ static int sampler_iterate_v2(bpa_sampler * s, unsigned iterations, bool in_kern
       HIPCHK(hipMemcpyAsync(s->v2_sp.p, &s->sp, sizeof(smp::Species), hipMemcpyHostToDevice, e->stream));
       s->v2_sp_sent = s->sp;
     }
-    if (s->env_dbg & 256u) HIPCHK(hipMemsetAsync(s->v2_declog.p, 0, 4*2048*sizeof(double), e->stream));
+    if (s->opt.debug & 256u) HIPCHK(hipMemsetAsync(s->v2_declog.p, 0, 4*2048*sizeof(double), e->stream));
     if (allloci)
     {
       // (a sweep-only launch draws nothing from the global stream and exchanges nothing)
@@ -2587,10 +2596,10 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
   s->host_current = false;
   if (s->big) return gb_iterate(s, iterations);
   if (s->generic) return gs_iterate(s, iterations);
-  if (s->v2_ok && !s->allreduce && !s->env_trace) return sampler_iterate_v2(s, iterations, true);
+  if (s->v2_ok && !s->allreduce && !s->opt.launch_times) return sampler_iterate_v2(s, iterations, true);
   if (s->kernel_bpp) return fail("bpa_sampler: BPP's proposal kernel runs in the persistent iteration kernel only (one GPU, or several with bpa_sampler_set_p2p)");
   // several ranks: the per-locus sweep by the persistent kernel (one launch), the all-loci steps one launch each
-  const bool v2_sweep = s->v2_ok && !s->env_trace;
+  const bool v2_sweep = s->v2_ok && !s->opt.launch_times;
   for (unsigned it = 0; it < iterations; ++it)
   {
     if (v2_sweep) { if (!sampler_iterate_v2(s, 1, false)) return 0; }
@@ -2656,13 +2665,13 @@ static int sampler_download(bpa_sampler * s)
   HIPCHK(hipStreamSynchronize(e->stream));
   if (s->v2_ok)
   {
-    if (s->env_dbg & 16u)
+    if (s->opt.debug & 16u)
     {
       double pr[16]; HIPCHK(hipMemcpy(pr, s->v2_prof.p, sizeof pr, hipMemcpyDeviceToHost));
       fprintf(stderr, "[smp2] cycles of lane 0 of workgroup 0, last launch: propose %.0f evaluate %.0f decide %.0f theta %.0f tau %.0f mix %.0f | exchange: theta %.0f tau+mix %.0f | inside the exchanges: first barrier %.0f sums %.0f barrier %.0f arrival + poll %.0f last barrier %.0f | of theta / tau / mix: the decision's arithmetic after the totals %.0f %.0f, MIX's re-draws inside the wait %.0f\n",
               pr[0], pr[1], pr[2], pr[3], pr[4], pr[5], pr[6], pr[7], pr[8], pr[9], pr[10], pr[11], pr[12], pr[13], pr[14], pr[15]);
       double p2[24]; HIPCHK(hipMemcpy(p2, s->v2_prof.p + 16 + s->v2_nwg, sizeof p2, hipMemcpyDeviceToHost));
-      if (s->v2_prog && (s->env_dbg & 64u))
+      if (s->v2_prog && (s->opt.debug & 64u))
         fprintf(stderr, "[smp2] inside the dummy exchanges (nobody late: the protocol alone): first barrier %.0f sums %.0f barrier %.0f arrival + poll %.0f last barrier %.0f\n", p2[0], p2[1], p2[2], p2[3], p2[4]);
       fprintf(stderr, "[smp2] sweep cycles of the waves of workgroup 0:");
       for (int w = 0; w < 8; ++w) fprintf(stderr, " %.0f", p2[8 + w]);
@@ -2678,7 +2687,7 @@ static int sampler_download(bpa_sampler * s)
       if (s->v2_prog)
         fprintf(stderr, "[smp2] (program-moves kernel: the numbers above are the control wave's — before B1 | wait for the loci | push | poll | THETA decision | TAU decisions | MIX decision | next proposal)\n");
     }
-    if (s->env_dbg & 256u)
+    if (s->opt.debug & 256u)
     {
       std::vector<double> r(4*2048); HIPCHK(hipMemcpy(r.data(), s->v2_declog.p, r.size()*sizeof(double), hipMemcpyDeviceToHost));
       for (unsigned k = 1000; k < 2048; ++k) if (r[4*k] != 0) fprintf(stderr, "[smp2dbg] %u: %g %.17g %.17g %.17g\n", k, r[4*k], r[4*k+1], r[4*k+2], r[4*k+3]);
@@ -2686,7 +2695,7 @@ static int sampler_download(bpa_sampler * s)
         fprintf(stderr, "[smp2] %s %d lnacc %.17g u %.17g -> %d\n", r[4*k] >= 300 ? "mix" : r[4*k] >= 200 ? "tau" : "theta",
                 (int)r[4*k] % 100, r[4*k + 1], r[4*k + 2], (int)r[4*k + 3]);
     }
-    if (s->env_dbg & 32u)
+    if (s->opt.debug & 32u)
     {
       std::vector<double> w(s->v2_nwg); HIPCHK(hipMemcpy(w.data(), s->v2_prof.p + 16, w.size()*sizeof(double), hipMemcpyDeviceToHost));
       double mn = 1e300, mx = 0, sm = 0; unsigned imx = 0;
@@ -2705,7 +2714,7 @@ static int sampler_download(bpa_sampler * s)
       // one-launch-per-step path, which needs no co-residency; this sampler keeps to that path from then on.
       const int zero2[2] = {0, 0};
       HIPCHK(hipMemcpy(s->v2_err.p, zero2, sizeof zero2, hipMemcpyHostToDevice));
-      if (s->p2p || verr[1] <= 0) return fail("bpa_sampler: the persistent iteration kernel timed out waiting for a workgroup's sum (is the device shared? BPA_SMP_V1=1 selects one launch per step)");
+      if (s->p2p || verr[1] <= 0) return fail("bpa_sampler: the persistent iteration kernel timed out waiting for a workgroup's sum (is the device shared? implementation = BPA_SAMPLER_SWEEP in the options, BPA_SMP_V1=1 in the environment, selects one launch per step)");
       fprintf(stderr, "[bpp_amd] the persistent iteration kernel timed out waiting for a workgroup (is the device shared?): %d iterations are run again\n", verr[1]);
       // The launches that did not run are the LAST ones of the log (a launch that finds the error word set gives up at once,
       // sweep2.hpp): they are taken off the counters and the host's copy of the global stream goes back to where the first of
@@ -2842,7 +2851,7 @@ extern "C" int bpa_sampler_kind(bpa_sampler_t * s)
   if (!sampler_upload(s)) return -1;
   if (s->big) return BPA_SAMPLER_BIG;
   if (s->generic) return BPA_SAMPLER_GENERIC;
-  if (s->v2_ok && !s->env_trace) return s->allreduce ? BPA_SAMPLER_HYBRID : BPA_SAMPLER_PERSISTENT;
+  if (s->v2_ok && !s->opt.launch_times) return s->allreduce ? BPA_SAMPLER_HYBRID : BPA_SAMPLER_PERSISTENT;
   return BPA_SAMPLER_SWEEP;
 }
 

@@ -290,7 +290,7 @@ int          bpa_batch_wait(bpa_engine_t *, double * lnl);
    (csrc/sweep2.hpp: the state of all loci stays in LDS for a whole call of bpa_sampler_iterate — many iterations —,
    a group of 8 or 16 lanes per locus runs the proposals, the all-loci decisions come from device-scope fixed-point
    accumulators inside the launch); with an all-reduce callback installed (several ranks), more loci than stay
-   resident at once or BPA_SMP_V1=1, the sweep kernel with one launch per step (csrc/sampler.hpp); otherwise — several rate categories, GTR, up to 16 tips, < 256
+   resident at once or implementation = BPA_SAMPLER_SWEEP in the options, the sweep kernel with one launch per step (csrc/sampler.hpp); otherwise — several rate categories, GTR, up to 16 tips, < 256
    patterns x categories — a generic path that proposes on the device and evaluates with the engine's batched step
    kernels (csrc/gsampler.hpp; 20-state loci too: their steps are written as the records of the tiled kernels); a
    4-state locus of more than 16 tips (<= 64), with scale buffers or as an unphased diploid makes it the big-tree path
@@ -298,6 +298,39 @@ int          bpa_batch_wait(bpa_engine_t *, double * lnl);
    scaling and phase averaging; one rank).  <= 15 populations.  Trees use the node numbering of a00_tree_t (tips first;
    arrays of 2*tips-1 entries); the species tree that of a00_set_species_tree.                                   */
 typedef struct bpa_sampler bpa_sampler_t;
+/* What a sampler is told at creation besides its loci.  bpa_sampler_options_from_env fills the struct (size included) from
+   the process environment — the only place the sampler code reads it, host-only, no device needed —, the caller overrides
+   what it wants, bpa_sampler_create_with takes the result; a sampler never looks at the environment again.  `size` is
+   sizeof(bpa_sampler_options) as the caller was compiled: fields are only ever added at the end, and a shorter struct gets
+   the defaults for the rest.  Field, default, the variable its default is read from:
+     implementation  BPA_SAMPLER_AUTO: every locus gets the implementation it fits (above).  BPA_SAMPLER_SWEEP: loci that fit
+                     the persistent kernel run the sweep kernel with one launch per step (BPA_SMP_V1).  BPA_SAMPLER_GENERIC:
+                     the generic sampler takes loci the LDS kernels would otherwise (BPA_SMP_GENERIC).  BPA_SAMPLER_BIG: the
+                     big-tree sampler takes every 4-state locus (BPA_SMP_BIG).  Several variables set: big, then generic.
+     composite       1: loci of several kinds get a part per kind (BPA_SAMPLER_COMPOSITE); 0 (BPA_SMP_NO_COMPOSITE): one plain
+                     sampler or a refusal.
+     chain           the generic sampler's GAGE + GSPR of every locus as one launch: -1 small JC69 sets only, 0 never, 1
+                     whenever possible (BPA_GS_CHAIN=0 / 1).
+     host_decisions  0; 1: the program's THETA / TAU / MIX of a generic sampler decided on the host (BPA_GS_HOSTDEC).
+   Diagnostics: debug, 0, the bit mask of csrc/sampler.hpp Args::dbg (BPA_SMP_DBG=mask); launch_times, 0, 1: per-launch times
+   on stderr, one launch per step (BPA_SMP_TRACE); inject, 0, k: the k-th persistent launch with all-loci steps gives up at its
+   first wait, inject_wg0 = 1: workgroup 0 alone (BPA_SMP_INJECT=k or k,w); diff, 0, 1: a generic sampler's GAGE / GSPR step by
+   both proposal kernels from the same state (BPA_GS_DIFF); decision_log, 0, 1: a generic sampler's host-taken decisions on
+   stderr, in the host driver's format (A00_DECLOG).                                                                      */
+#define BPA_SAMPLER_AUTO (-1)
+typedef struct bpa_sampler_options
+{
+  unsigned size;
+  int implementation, composite, chain, host_decisions;
+  unsigned debug;
+  int launch_times;
+  long inject;
+  int inject_wg0, diff, decision_log;
+} bpa_sampler_options;
+void bpa_sampler_options_from_env(bpa_sampler_options *);
+bpa_sampler_t * bpa_sampler_create_with(bpa_engine_t *, bpa_locus_t * const * loci, unsigned nloci,
+                                        unsigned long seed, const bpa_sampler_options *);
+/* bpa_sampler_options_from_env, then bpa_sampler_create_with */
 bpa_sampler_t * bpa_sampler_create(bpa_engine_t *, bpa_locus_t * const * loci, unsigned nloci,
                                    unsigned long seed);
 void bpa_sampler_destroy(bpa_sampler_t *);
@@ -322,7 +355,7 @@ void bpa_sampler_set_finetune(bpa_sampler_t *, double gage, double gspr, double 
    A sampler the rule cannot run on (loci of several kinds, a generic or big-tree sampler without the program's moves)
    fails BEFORE any iteration has run.
    Where: the persistent iteration kernel (device counters by move type), and the generic and the big-tree sampler with the
-   program's moves (the trees carry the age / prune-regraft counts, the decisions' state on the device — or, BPA_GS_HOSTDEC,
+   program's moves (the trees carry the age / prune-regraft counts, the decisions' state on the device — or, host_decisions,
    the host — those of tau, mixing and the theta window).  Several ranks: the per-locus moves' counts
    are pooled over the ranks first (the callback, or the mailboxes' one-shot exchange), so every rank ends at the same step
    lengths, the whole data set's — every rank calls it at the same point of its run.                                      */
@@ -377,7 +410,7 @@ int  bpa_sampler_set_proposal_kernel(bpa_sampler_t *, int kind);
    synchronisation inside an iteration (several ranks: the sums pass through the all-reduce callback on the stream first, so
    with a stream-ordered collective none either).  The big-tree sampler (up to 64 tips, scalers, diploid loci; one rank) does
    the same with its own step kernel (gbig::big_step_kernel<true>): the loci bring their Jacobian and, for TAU, the T2h of the
-   three populations after the move; it has the device-decided form only.  BPA_GS_HOSTDEC=1 keeps round 5's form on the
+   three populations after the move; it has the device-decided form only.  host_decisions = 1 in the options keeps round 5's form on the
    generic sampler:
    the sums come to the HOST — 24 to 72 bytes and one synchronisation per all-loci step — which takes the
    decision with the statements of a00_driver.c (theta_step_gibbs / tau_step / mix_step) and sends it back as a one-lane
@@ -393,8 +426,8 @@ void bpa_sampler_set_theta_prior(bpa_sampler_t *, double alpha, double beta, dou
    default, 'thetaprior = invgamma a b e' / 'tauprior = invgamma a b' (a00_set_prior_kinds; the arithmetic is in
    bpp_amd_host.h).  Before bpa_sampler_initialize; 0 + bpa_last_error on refusal.  Honoured by the generic sampler (both
    move sets, device- and host-decided), the big-tree sampler (both move sets) and the one-launch-per-step sampler.
-   Refused: the persistent kernel, which has the gamma priors only (loci that fit it get it: BPA_SMP_GENERIC=1 or
-   BPA_SMP_V1=1 at creation is the way out); loci of several kinds; a sampler with an all-reduce callback or mailboxes
+   Refused: the persistent kernel, which has the gamma priors only (loci that fit it get it: implementation =
+   BPA_SAMPLER_GENERIC or BPA_SAMPLER_SWEEP in bpa_sampler_create_with's options is the way out); loci of several kinds; a sampler with an all-reduce callback or mailboxes
    installed (and installing one after an inverse gamma was chosen); a kind other than the two; a call after
    bpa_sampler_initialize.  A sampler that never calls this runs exactly as it did.                                       */
 #define BPA_PRIOR_GAMMA    0
@@ -443,7 +476,7 @@ int  bpa_sampler_get_tree_msc(bpa_sampler_t *, unsigned i, int * pop, double * l
 int  bpa_sampler_summary(bpa_sampler_t *, double * total_lnl, unsigned long * proposals,
                          unsigned long * accepted, unsigned long * launches);
 /* The sample trace: what BPP writes to mcmc.txt every `sampfreq` iterations (taus, thetas, lnL), recorded on the device while
-   the chain runs — no download, no copy of the trees, no wait for the stream per sample.  (Not the BPA_SMP_TRACE diagnostic.)
+   the chain runs — no download, no copy of the trees, no wait for the stream per sample.  (Not the launch_times diagnostic.)
      bpa_sampler_set_trace    every = 0: off, buffers freed, unread rows dropped.  Otherwise a row is recorded after iterations
                               every, 2 every, ... of bpa_sampler_iterate, counted from this call; the count carries over from
                               one bpa_sampler_iterate to the next and does not advance inside bpa_sampler_burnin (which writes
@@ -506,7 +539,7 @@ void bpa_sampler_set_subst_moves(bpa_sampler_t *, double ft_freqs, double ft_qra
    them fixed: the program's rates from a file); widths 0 = that move is off (default: both off), changeable at any time;
    mubar > 0 sets the mean, 0 keeps the current one; counters: index 0 = MUI, 1 = MUBAR, apart from bpa_sampler_summary's
    totals.  A sampler on which none of this is called computes what it always did, to the bit.
-   The generic and the big-tree sampler (BPA_SAMPLER_GENERIC, BPA_SAMPLER_BIG; BPA_SMP_GENERIC=1 makes the generic sampler take
+   The generic and the big-tree sampler (BPA_SAMPLER_GENERIC, BPA_SAMPLER_BIG; implementation = BPA_SAMPLER_GENERIC in the options makes the generic sampler take
    loci the LDS kernels would otherwise; the big-tree sampler reads the counters off its own trees and settles a MUI step that
    closes an iteration in the next iteration's first launch, as the generic sampler does): rates or a non-zero width on the
    persistent / sweep and the composite samplers fail, as do a rate <= 0 or not finite, a_mui <= 0 while a move is on, rates
@@ -533,7 +566,7 @@ int  bpa_sampler_locusrate_counters(bpa_sampler_t *, unsigned long prop[2], unsi
    time; the counters are apart from bpa_sampler_summary's totals (bpa_sampler_burnin does not adapt ft_h: apply
    bpa_finetune_onestep to them).  Heredity scalars and locus rates may be on together.  A sampler on which none of this is
    called computes what it always did, to the bit.
-   The generic and the big-tree sampler (BPA_SAMPLER_GENERIC, BPA_SAMPLER_BIG; BPA_SMP_GENERIC=1 makes the generic sampler take
+   The generic and the big-tree sampler (BPA_SAMPLER_GENERIC, BPA_SAMPLER_BIG; implementation = BPA_SAMPLER_GENERIC in the options makes the generic sampler take
    loci the LDS kernels would otherwise — autosomal, X-linked and mitochondrial loci of many sequences each are the big-tree
    sampler's): scalars or a non-zero width on the persistent / sweep and the composite samplers fail (a width of 0 is "nothing asked for": 1), as do a scalar <= 0 or not finite, a or
    b <= 0 while the move is on, scalars after bpa_sampler_initialize, and — when bpa_sampler_iterate is called, before any

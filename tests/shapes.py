@@ -224,6 +224,17 @@ def case(name):
     return _SETS[name]
 
 
+OPTION_IDS = {"one_call": "ONE_CALL", "chain": "BPA_GS_CHAIN", "host_decisions": "BPA_GS_HOSTDEC"}
+
+
+def option_id(v):
+    """ids= of a parametrisation whose cases carry bpp_amd.Sampler options as a dict (next to test-side switches such as
+    one_call): the name the case has always had, that of the variable the option's default is read from"""
+    if not isinstance(v, dict):
+        return None
+    return "+".join(OPTION_IDS[k] if k == "one_call" else f"{OPTION_IDS[k]}={int(x)}" for k, x in v.items())
+
+
 def configure(drv, c, moves, host=False):
     """species tree, tips' species, priors, step lengths and the moves ('uniform', 'bpp', 'program') of case c on a
     hostdrv.Driver (host=True) or a bpp_amd.Sampler — the same calls on both, so that they walk the same chain"""

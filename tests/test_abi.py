@@ -145,6 +145,22 @@ def test_the_default_build_reads_few_switches_from_the_environment():
             for m in re.finditer(r"(?<![A-Za-z_])getenv\(\"([A-Z0-9_]+)\"\)", line):
                 sites.append((os.path.relpath(f, ROOT), n, m.group(1)))
     assert len(sites) <= 15, sites
+    # the sampler code reads the environment in ONE function, bpa_sampler_options_from_env (include/bpp_amd.h): a sampler is told
+    # everything else through its options
+    inside = 0
+    for f in sorted(sum((glob.glob(os.path.join(csrc, g)) for g in ("sampler.hpp", "sweep2.hpp", "gsampler*.hpp", "bigsampler*.hpp", "composite.hpp")), [])):
+        text = "".join("\n" if l.strip().startswith(("//", "/*", "*")) else l for l in open(f))
+        lo = hi = -1
+        m = re.search(r"void bpa_sampler_options_from_env\([^)]*\)\s*\{", text)
+        if m:
+            lo, depth, hi = m.end(), 1, m.end()
+            while depth:
+                depth += {"{": 1, "}": -1}.get(text[hi], 0)
+                hi += 1
+        for g in re.finditer(r"(?<![A-Za-z_])getenv\b", text):
+            assert lo <= g.start() < hi, (os.path.relpath(f, ROOT), text.count("\n", 0, g.start()) + 1)
+            inside += 1
+    assert inside >= 11
     for top in ("bpp_amd", "include", "integration"):
         for d, _, files in os.walk(os.path.join(ROOT, top)):
             for name in files:

@@ -39,14 +39,12 @@ def _finish(host, dev, tau0, thetas, taus_moved=True):
 
 
 @pytest.mark.parametrize("taxa,model,R,nloci,iters,scaling", [(4, "jc69", 1, 150, 5, False), (8, "gtr", 4, 30, 3, False), (8, "jc69", 1, 30, 3, True)])
-def test_big_sampler_program_moves_forced_on_small_loci_equals_host_driver(taxa, model, R, nloci, iters, scaling, monkeypatch):
+def test_big_sampler_program_moves_forced_on_small_loci_equals_host_driver(taxa, model, R, nloci, iters, scaling):
     """the shapes, priors and step lengths of test_gpu_bigsampler.py::test_big_sampler_forced_on_small_loci_equals_host_driver"""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 300, taxa, model, R, seed=19)
     host = hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data, scaling), data, seed=29, scaling=scaling)
-    monkeypatch.setenv("BPA_SMP_BIG", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data, scaling), data, seed=29)
-    monkeypatch.delenv("BPA_SMP_BIG")
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data, scaling), data, seed=29, implementation="big")
     parent, tau0, thetas = synth.species_tree_arrays(taxa)
     for drv in (host, dev):
         _program(drv)

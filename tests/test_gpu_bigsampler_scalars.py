@@ -101,7 +101,7 @@ TRAJECTORIES = [
 
 
 @pytest.mark.parametrize("name,moves,iters,one_call", TRAJECTORIES)
-def test_big_tree_sampler_with_scalars_equals_host_driver(name, moves, iters, one_call, monkeypatch):
+def test_big_tree_sampler_with_scalars_equals_host_driver(name, moves, iters, one_call):
     """rates log-uniform on (0.5, 2), scalars on (0.25, 2), HRDT + MUI + MUBAR on together (one_call: MUBAR off): the decisions,
     both counter families, trees, populations and buffer indices of the host driver's hered_step / mui_step / mubar_step in
     a00_iterate's order, through heredity.walk at its own bars — ages, taus, thetas 1e-12 with uniform windows (scalars ==),
@@ -112,10 +112,7 @@ def test_big_tree_sampler_with_scalars_equals_host_driver(name, moves, iters, on
     eng = bpp_amd.Engine(0)
     loci_of = make or (lambda e: tape.make_engine_loci(e, data, c["scaling"]))
     host = HD.HeredDriver(hostdrv.hip_driver(eng, loci_of(eng), data, seed=31, scaling=c["scaling"]))
-    if forced:
-        monkeypatch.setenv("BPA_SMP_BIG", "1")
-    dev = bpp_amd.Sampler(eng, loci_of(eng), data, seed=31)
-    monkeypatch.delenv("BPA_SMP_BIG", raising=False)
+    dev = bpp_amd.Sampler(eng, loci_of(eng), data, seed=31, implementation="big" if forced else None)
     ft = (RATE_FT[0], 0.0) if one_call else RATE_FT
     for drv, is_host in ((host, True), (dev, False)):
         rates, h0 = _configure(drv, c, moves, is_host, ft, name == "frogs")
@@ -284,7 +281,7 @@ def test_state_invariants_after_a_long_run_with_scalars(moves):
 # ------------------------------------------------------------------ 4. prior only
 @pytest.mark.parametrize("which", ["heredity", "rates"])
 @pytest.mark.parametrize("moves", ["uniform", "program"])
-def test_prior_only_run_on_the_big_tree_sampler_leaves_every_prior(moves, which, monkeypatch):
+def test_prior_only_run_on_the_big_tree_sampler_leaves_every_prior(moves, which):
     """usedata = 0 on the data, priors, step lengths and run length (500 + 2 000 x 3 iterations) of
     tests/test_gpu_heredity.py::test_prior_only_run_on_the_device_leaves_every_prior, the loci forced onto the big-tree sampler:
     heredity — every h_i ~ gamma(4, 4), every theta and the root's tau their own priors (heredity.prior_marginals); rates —
@@ -296,9 +293,7 @@ def test_prior_only_run_on_the_big_tree_sampler_leaves_every_prior(moves, which,
     data = shapes.shaped_set(sp, stree, [20 + k for k in range(12)], 85, model="gtr", rate_cats=4)
     eng = bpp_amd.Engine(0)
     eng.set_options(usedata=0, bfbeta=1.0)
-    monkeypatch.setenv("BPA_SMP_BIG", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=17)
-    monkeypatch.delenv("BPA_SMP_BIG")
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=17, implementation="big")
     if moves == "program":
         dev.set_proposal_kernel(1)
         dev.set_program_moves(True, 0.3)
@@ -401,7 +396,7 @@ def test_what_the_big_tree_sampler_refuses():
     comp.set_species_tree(parent, tau0, thetas)
     for call in (lambda: comp.set_locus_rates(np.full(len(mixed), 1.5)), lambda: comp.set_locusrate_moves(0.5, 0.0, 5.0),
                  lambda: comp.set_heredity(np.full(len(mixed), 0.75)), lambda: comp.set_heredity_move(0.5, 4.0, 4.0)):
-        with pytest.raises(bpp_amd.BpaError, match="generic and the big-tree sampler only.*composite.*BPA_SMP_GENERIC=1"):
+        with pytest.raises(bpp_amd.BpaError, match="generic and the big-tree sampler only.*composite.*implementation = BPA_SAMPLER_GENERIC in the options"):
             call()
     assert comp.kind() == "composite"
     comp.close(); eng.close()

@@ -56,7 +56,7 @@ TRAJECTORIES = [
     ("17-g4", "program", False, False),
     ("17-g4", "uniform", True, False),                     # HRDT, the nine parameter steps, MUI, MUBAR: a00_iterate's tail
     ("17-g4", "program", True, False),
-    ("forced-8-gtr", "program", False, False),             # 8-tip loci forced onto the big-tree sampler (BPA_SMP_BIG)
+    ("forced-8-gtr", "program", False, False),             # 8-tip loci forced onto the big-tree sampler (implementation="big")
     ("17-g1", "uniform", False, False),                    # ONE rate category: the alpha move proposes nothing, draws nothing
     ("17-g1", "program", False, False),
     ("17-g4", "uniform", False, True),                     # the alpha step closes the iteration: settled inside the next one's first launch
@@ -65,7 +65,7 @@ TRAJECTORIES = [
 
 
 @pytest.mark.parametrize("name,moves,tail,one_call", TRAJECTORIES)
-def test_big_tree_sampler_with_subst_moves_equals_host_driver(name, moves, tail, one_call, monkeypatch):
+def test_big_tree_sampler_with_subst_moves_equals_host_driver(name, moves, tail, one_call):
     """3 iterations with the widths and the alpha prior of locusrates.configure (0.3, 0.4, 0.8; gamma(1, 1); alpha starts at
     0.5): decisions and counters equal after every iteration (one_call: at the end), trees, populations and buffer indices
     equal at the end; total lnL 1e-10, ages, taus, thetas 1e-12 with uniform windows and 1e-9 with the program's moves,
@@ -76,10 +76,7 @@ def test_big_tree_sampler_with_subst_moves_equals_host_driver(name, moves, tail,
     data, n = c["data"], len(c["data"])
     eng = bpp_amd.Engine(0)
     host = HD.HeredDriver(hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data), data, seed=31))
-    if forced:
-        monkeypatch.setenv("BPA_SMP_BIG", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=31)
-    monkeypatch.delenv("BPA_SMP_BIG", raising=False)
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=31, implementation="big" if forced else None)
     tol = 1e-12 if moves == "uniform" else 1e-9
     if tail:
         h0 = HD.start_scalars(n)
@@ -267,7 +264,7 @@ def batch_lnl(eng, loc, d, t, mui):
 
 # ------------------------------------------------------------------ 4. prior only
 @pytest.mark.parametrize("moves", ["uniform", "program"])
-def test_prior_only_run_leaves_alpha_its_prior_and_the_simplex(moves, monkeypatch):
+def test_prior_only_run_leaves_alpha_its_prior_and_the_simplex(moves):
     """usedata = 0 on 6 GTR+Gamma4 8-tip loci forced onto the big-tree sampler, 300 + 2 000 x 2 iterations: every locus's alpha ~
     gamma(4, 8) under a window of 1.5 (locusrates.gamma_check: mean within 4.5 batch-means standard errors, sd within (0.8, 1.2)
     of the prior's); at every sample the frequencies sum to 1 within 1e-12 with every component >= 1e-5, the exchangeabilities
@@ -286,9 +283,7 @@ def test_prior_only_run_leaves_alpha_its_prior_and_the_simplex(moves, monkeypatc
     n = len(data)
     eng = bpp_amd.Engine(0)
     eng.set_options(usedata=0, bfbeta=1.0)
-    monkeypatch.setenv("BPA_SMP_BIG", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=17)
-    monkeypatch.delenv("BPA_SMP_BIG")
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=17, implementation="big")
     if moves == "program":
         dev.set_proposal_kernel(1)
         dev.set_program_moves(True, 0.3)

@@ -1,4 +1,4 @@
-"""The persistent kernel's exchange on every shard layout (csrc/sweep2.hpp: xlayout, xpush, xpoll; BPA_SMP_DBG bits 16-18 choose
+"""The persistent kernel's exchange on every shard layout (csrc/sweep2.hpp: xlayout, xpush, xpoll; the sampler's debug bits 16-18 choose
 the shards of an accumulator set: 1 .. 4 = 8, 16, 32, 64).  The totals are fixed-point integer sums, so which line a workgroup's
 sums went to must not show in any bit of any result: the device against the C host driver on the same seed, and every layout
 against the 8 shards the kernel started with.
@@ -6,7 +6,7 @@ against the 8 shards the kernel started with.
 Loci (eight four-taxon loci to a wave, four waves of loci a workgroup where the loci leave a CU to every workgroup): 8, 264 and
 2 100 are 1, 9 and 66 workgroups — fewer workgroups than shards, more than 8 and no multiple of it, more than 64 and no multiple
 of it.  Eight taxa: seven thetas are 14 + 5 = 19 sums, an exchange of two blocks, which uses both accumulator sets.
-BPA_SMP_DBG & 64 adds a dummy exchange (zeros) behind every real one: it takes its turn with the two sets and must leave the
+debug & 64 adds a dummy exchange (zeros) behind every real one: it takes its turn with the two sets and must leave the
 chain as it is; 16 prints workgroup 0's counters, among them the waves of loci a workgroup."""
 import importlib.util
 import os
@@ -57,9 +57,8 @@ def _data(taxa, nloci):
     return synth.make_dataset(nloci, 300, taxa, "jc69", 1, seed=2801 if nloci == 2100 else 700 + nloci)
 
 
-def _device(eng, data, taxa, monkeypatch, dbg, **kw):
-    monkeypatch.setenv("BPA_SMP_DBG", str(dbg))           # (read when the sampler is created)
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=5)
+def _device(eng, data, taxa, dbg, options={}, **kw):
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=5, debug=dbg, **options)
     _setup(dev, taxa, **kw)
     assert dev.kind() == "persistent"
     return dev
@@ -110,10 +109,10 @@ def _same_bits(got, want):
         assert got[k].shape == want[k].shape and (got[k] == want[k]).all(), k
 
 
-def _eight_shards(eng, taxa, nloci, monkeypatch, tmp_path, rec=None):
+def _eight_shards(eng, taxa, nloci, tmp_path, rec=None):
     """the 8-shard run's arrays (checked against the host's record where one is given)"""
     if (taxa, nloci) not in _dumps:
-        dev = _device(eng, _data(taxa, nloci), taxa, monkeypatch, SHARDS[8])
+        dev = _device(eng, _data(taxa, nloci), taxa, SHARDS[8])
         _run(dev, nloci, rec)
         _dumps[(taxa, nloci)] = _dump(dev, nloci, tmp_path / "s8")
         dev.close()
@@ -121,15 +120,15 @@ def _eight_shards(eng, taxa, nloci, monkeypatch, tmp_path, rec=None):
 
 
 @pytest.mark.parametrize("nloci", [8, 264, 2100])
-def test_every_layout_gives_the_host_drivers_chain_and_the_same_bits(nloci, monkeypatch, tmp_path, capfd):
+def test_every_layout_gives_the_host_drivers_chain_and_the_same_bits(nloci, tmp_path, capfd):
     """(a) four taxa, BPP's kernel and the program's moves: 8 and 64 shards against the host driver; 16, 32 and 64 equal to 8 to the bit"""
     eng = bpp_amd.Engine(0)
     data = _data(4, nloci)
     rec = _host_record(eng, data, 4, nloci)
     _dumps.pop((4, nloci), None)
-    want = _eight_shards(eng, 4, nloci, monkeypatch, tmp_path, rec)
+    want = _eight_shards(eng, 4, nloci, tmp_path, rec)
     for S in (16, 32, 64):
-        dev = _device(eng, data, 4, monkeypatch, SHARDS[S] | (COUNTERS if S == 64 else 0))
+        dev = _device(eng, data, 4, SHARDS[S] | (COUNTERS if S == 64 else 0))
         _run(dev, nloci, rec if S == 64 else None)
         _same_bits(_dump(dev, nloci, tmp_path / f"s{S}"), want)
         dev.close()
@@ -137,37 +136,37 @@ def test_every_layout_gives_the_host_drivers_chain_and_the_same_bits(nloci, monk
     eng.close()
 
 
-def test_two_blocks_use_both_sets_within_one_exchange(monkeypatch, tmp_path):
+def test_two_blocks_use_both_sets_within_one_exchange(tmp_path):
     """(b) eight taxa: 19 sums = two blocks an exchange; 64 shards against the host driver, and equal to 8 shards to the bit"""
     eng = bpp_amd.Engine(0)
     nloci = 20
     data = _data(8, nloci)
     rec = _host_record(eng, data, 8, nloci)
-    want = _eight_shards(eng, 8, nloci, monkeypatch, tmp_path)
-    dev = _device(eng, data, 8, monkeypatch, SHARDS[64])
+    want = _eight_shards(eng, 8, nloci, tmp_path)
+    dev = _device(eng, data, 8, SHARDS[64])
     _run(dev, nloci, rec)
     _same_bits(_dump(dev, nloci, tmp_path / "s64"), want)
     dev.close(); eng.close()
 
 
-def test_uniform_windows_every_wave_zero_polls(monkeypatch):
+def test_uniform_windows_every_wave_zero_polls():
     """(c) iter_kernel<4, false>: no control wave — wave 0 of every workgroup polls between the workgroup's barriers"""
     eng = bpp_amd.Engine(0)
     nloci = 40
     data = _data(4, nloci)
     rec = _host_record(eng, data, 4, nloci, program=False, bpp=False)
-    dev = _device(eng, data, 4, monkeypatch, SHARDS[64], program=False, bpp=False)
+    dev = _device(eng, data, 4, SHARDS[64], program=False, bpp=False)
     _run(dev, nloci, rec, gibbs=False)
     dev.close(); eng.close()
 
 
 @pytest.mark.parametrize("S", [0, 64])
-def test_the_dummy_exchange_leaves_the_chain_as_it_is(S, monkeypatch, tmp_path):
-    """(d) 264 loci with BPA_SMP_DBG & 64 — on the default layout and on 64 shards — equal to the bit to 8 shards without it"""
+def test_the_dummy_exchange_leaves_the_chain_as_it_is(S, tmp_path):
+    """(d) 264 loci with debug & 64 — on the default layout and on 64 shards — equal to the bit to 8 shards without it"""
     eng = bpp_amd.Engine(0)
     nloci = 264
-    want = _eight_shards(eng, 4, nloci, monkeypatch, tmp_path)
-    dev = _device(eng, _data(4, nloci), 4, monkeypatch, DUMMY | (SHARDS[S] if S else 0))
+    want = _eight_shards(eng, 4, nloci, tmp_path)
+    dev = _device(eng, _data(4, nloci), 4, DUMMY | (SHARDS[S] if S else 0))
     _run(dev, nloci)
     _same_bits(_dump(dev, nloci, tmp_path / "dummy"), want)
     dev.close(); eng.close()

@@ -12,6 +12,7 @@ from bpp_amd import synth
 import oraclelib as O
 import hostdrv
 import tape
+import shapes
 from common import rel
 
 pytestmark = pytest.mark.gpu
@@ -43,29 +44,22 @@ def walk(host, dev, iters, nloci, check_every=1, tol=1e-12, each=None):
         assert rel(a["lnl"], b["lnl"]) < 10*tol and rel(a["logpr"], b["logpr"]) < 10*tol
 
 
-@pytest.mark.parametrize("taxa,model,R,nloci,iters,forced,chain", [(4, "jc69", 1, 300, 5, True, None), (8, "gtr", 4, 60, 3, False, "1"), (8, "gtr", 4, 60, 3, False, "0"),
-                                                                   (8, "gtr", 4, 700, 2, False, "0"), (8, "gtr", 4, 700, 2, False, "1"), (8, "jc69", 1, 40, 3, True, "0"),
+@pytest.mark.parametrize("taxa,model,R,nloci,iters,forced,chain", [(4, "jc69", 1, 300, 5, True, None), (8, "gtr", 4, 60, 3, False, 1), (8, "gtr", 4, 60, 3, False, 0),
+                                                                   (8, "gtr", 4, 700, 2, False, 0), (8, "gtr", 4, 700, 2, False, 1), (8, "jc69", 1, 40, 3, True, 0),
                                                                    (8, "jc69", 1, 40, 3, True, None), (6, "lg", 4, 40, 3, False, None), (6, "lg", 1, 24, 2, False, None),
                                                                    (6, "lg", 4, 300, 2, False, None)])
-def test_generic_sampler_equals_host_driver(taxa, model, R, nloci, iters, forced, chain, monkeypatch):
+def test_generic_sampler_equals_host_driver(taxa, model, R, nloci, iters, forced, chain):
     """(lg: amino-acid loci — BASELINE config 4's kind —, the steps written on the device as the records of the tiled 20-state
     kernels: pmatrix_wg2_kernel, partials_lnl_pipe20_kernel; 700 GTR loci: enough workgroups of the packing for the per-locus
     steps to run as two half-batches on two streams — more launches, the same trajectory; 300 amino-acid loci: the 20-state
     form of the same, two halves of the loci; chain None: the per-locus steps
-    as ONE launch (gsm2::gchain_kernel: the default for small JC69 sets, "1": forced), "0": a launch per step (BPA_GS_CHAIN))"""
-    if chain is not None:
-        monkeypatch.setenv("BPA_GS_CHAIN", chain)
+    as ONE launch (gsm2::gchain_kernel: the default for small JC69 sets, 1: forced), 0: a launch per step (the sampler's chain option))"""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 300, taxa, model, R, seed=19)
     loci_a = tape.make_engine_loci(eng, data)
     loci_b = tape.make_engine_loci(eng, data)
     host = hostdrv.hip_driver(eng, loci_a, data, seed=29)
-    if forced:
-        os.environ["BPA_SMP_GENERIC"] = "1"            # these loci would fit the sweep kernel
-    try:
-        dev = bpp_amd.Sampler(eng, loci_b, data, seed=29)
-    finally:
-        os.environ.pop("BPA_SMP_GENERIC", None)
+    dev = bpp_amd.Sampler(eng, loci_b, data, seed=29, implementation="generic" if forced else None, chain=chain)      # (forced: these loci would fit the sweep kernel)
     parent, tau0, thetas = synth.species_tree_arrays(taxa)
     for drv in (host, dev):
         drv.set_species_tree(parent, tau0, thetas)
@@ -85,12 +79,12 @@ def test_generic_sampler_equals_host_driver(taxa, model, R, nloci, iters, forced
         assert rel(have, full) < 1e-12 and rel(t["lnl"], full) < 1e-12
     w = dev.work()
     assert w["sweeps"] >= iters*(3*taxa - 3) and w["node_updates"] > 0 and w["bytes"] > 0      # (generic path: evaluated steps)
-    if model == "gtr" and chain == "0":
+    if model == "gtr" and chain == 0:
         assert (w["sweeps"] >= iters*2*(3*taxa - 3)) == (nloci >= 700) == (dev.streams() == 2)   # two half-batch launches per per-locus step
     if model == "lg":
         assert (dev.streams() == 2) == (nloci >= 128)
     if model != "lg":
-        assert (dev.summary()["launches"] < iters*2*(3*taxa - 3)) == (chain != "0")             # the chain: one launch for the per-locus steps (else >= 2 each)
+        assert (dev.summary()["launches"] < iters*2*(3*taxa - 3)) == (chain != 0)             # the chain: one launch for the per-locus steps (else >= 2 each)
     dev.close(); host.close(); eng.close()
 
 
@@ -262,25 +256,21 @@ def test_loci_of_several_kinds_in_one_sampler():
                                                                 (8, "jc69", 1, 40, 4, False, None),
                                                                 # the all-loci decisions on the HOST (round 5's form, the trajectory reference of
                                                                 # the device's gdec_kernel, which is the default since round 6)
-                                                                (8, "gtr", 4, 60, 4, True, "BPA_GS_HOSTDEC=1"), (6, "lg", 4, 40, 3, False, "BPA_GS_HOSTDEC=1")])
-def test_generic_sampler_with_the_program_s_moves_equals_host_driver(taxa, model, R, nloci, iters, subst, env, monkeypatch):
+                                                                (8, "gtr", 4, 60, 4, True, dict(host_decisions=True)), (6, "lg", 4, 40, 3, False, dict(host_decisions=True))],
+                         ids=shapes.option_id)
+def test_generic_sampler_with_the_program_s_moves_equals_host_driver(taxa, model, R, nloci, iters, subst, env):
     """BPP's own iteration on the generic sampler (bpa_sampler_set_proposal_kernel(BPP) + bpa_sampler_set_program_moves): the
     per-locus proposals draw from the reference's generator with its Bactrian-Laplace windows and acceptance rule on the device
     (gsm2::gstep2_kernel<.., BPP>), THETA by the metropolized Gibbs draw, the thetas re-drawn inside the rubber band and the
     mixing step — decided ON THE DEVICE by one wave from the loci's sums (gsm::gdec_kernel: the persistent kernel's control-wave
-    functions; round 6) or, BPA_GS_HOSTDEC=1, on the host (gs_prog_theta / _tau / _mix, the statements of theta_step_gibbs /
+    functions; round 6) or, host_decisions=True, on the host (gs_prog_theta / _tau / _mix, the statements of theta_step_gibbs /
     tau_step / mix_step of a00_driver.c).  Same trajectory as the C host driver with a00_set_program_moves on the same library."""
-    if model == "jc69":
-        monkeypatch.setenv("BPA_SMP_GENERIC", "1")
-    if env:
-        monkeypatch.setenv(*env.split("="))
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 300, taxa, model, R, seed=41)
     loci_a = tape.make_engine_loci(eng, data)
     loci_b = tape.make_engine_loci(eng, data)
     host = hostdrv.hip_driver(eng, loci_a, data, seed=43)
-    dev = bpp_amd.Sampler(eng, loci_b, data, seed=43)
-    monkeypatch.delenv("BPA_SMP_GENERIC", raising=False)
+    dev = bpp_amd.Sampler(eng, loci_b, data, seed=43, implementation="generic" if model == "jc69" else None, **(env or {}))
     parent, tau0, thetas = synth.species_tree_arrays(taxa)
     for drv in (host, dev):
         drv.set_proposal_kernel(1)

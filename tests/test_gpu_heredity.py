@@ -10,43 +10,39 @@ from bpp_amd import synth
 import tape
 import locusrates as LR
 import heredity as HD
+import shapes
 
 pytestmark = pytest.mark.gpu
 
 
-def _pair(c, seed, monkeypatch, generic=False, env=None):
+def _pair(c, seed, generic=False, **options):
     """(engine, engine loci of the device sampler, host driver, device sampler) on case c's data"""
-    if env:
-        monkeypatch.setenv(*env.split("="))
     eng = bpp_amd.Engine(0)
     data = c["data"]
     loci_a = tape.make_engine_loci(eng, data)
     loci_b = tape.make_engine_loci(eng, data)
     host = HD.hip_driver(eng, loci_a, data, seed=seed)
-    if generic:
-        monkeypatch.setenv("BPA_SMP_GENERIC", "1")
-    dev = bpp_amd.Sampler(eng, loci_b, data, seed=seed)
-    monkeypatch.delenv("BPA_SMP_GENERIC", raising=False)
+    dev = bpp_amd.Sampler(eng, loci_b, data, seed=seed, implementation="generic" if generic else None, **options)
     return eng, loci_b, host, dev
 
 
-# case, moves, iterations, environment, the rate moves on as well
+# case, moves, iterations, options, the rate moves on as well
 TRAJECTORIES = [
     ("a", "uniform", 5, None, False),                      # 70 loci forced generic: two workgroups of gstep_kernel; the chain launch
-    ("a", "uniform", 5, "BPA_GS_CHAIN=0", False),          # ... and a launch per step
+    ("a", "uniform", 5, dict(chain=False), False),          # ... and a launch per step
     ("a", "program", 3, None, False),                      # BPP's kernel, THETA / TAU / MIX decided on the device from the sums of T2h/h
-    ("a", "program", 3, "BPA_GS_HOSTDEC=1", False),        # ... and on the host
+    ("a", "program", 3, dict(host_decisions=True), False),        # ... and on the host
     ("b", "uniform", 5, None, False),                      # two part-batches, fuse_pm, the substitution moves after HRDT
     ("b", "program", 3, None, False),
     ("b", "uniform", 5, None, True),                       # ... with MUI and MUBAR
     ("c", "uniform", 5, None, False),                      # 16 tips: 32-lane groups
     ("c", "program", 3, None, False),
-    ("b", "uniform", 5, "ONE_CALL", False),                # all iterations in one iterate call
+    ("b", "uniform", 5, dict(one_call=True), False),                # all iterations in one iterate call
 ]
 
 
-@pytest.mark.parametrize("name,moves,iters,env,rates", TRAJECTORIES)
-def test_device_sampler_with_heredity_equals_host_driver(name, moves, iters, env, rates, monkeypatch):
+@pytest.mark.parametrize("name,moves,iters,env,rates", TRAJECTORIES, ids=shapes.option_id)
+def test_device_sampler_with_heredity_equals_host_driver(name, moves, iters, env, rates):
     """scalars log-uniform on (0.25, 2), HRDT on: same decisions, counters (the sampler's and HRDT's), trees and buffer indices
     as the host driver's hered_step and its densities at h_i theta; ages, taus, thetas and scalars to locusrates.walk's bars
     (1e-12 uniform — the scalars ==: h' = |h + ft_h (u - 1/2)| involves no libm —, 1e-9 with the program's moves), logpr to
@@ -54,8 +50,9 @@ def test_device_sampler_with_heredity_equals_host_driver(name, moves, iters, env
     c = LR.case(name)
     n = len(c["data"])
     subst = name == "b"
-    one_call = env == "ONE_CALL"
-    eng, loci, host, dev = _pair(c, 31, monkeypatch, generic=name == "a", env=None if one_call else env)
+    env = dict(env or {})
+    one_call = env.pop("one_call", False)
+    eng, loci, host, dev = _pair(c, 31, generic=name == "a", **env)
     h0 = HD.start_scalars(n)
     for drv, is_host in ((host, True), (dev, False)):
         HD.configure(drv, c, moves, is_host, subst=subst, rates=rates, scalars=h0)
@@ -168,9 +165,9 @@ def test_what_the_device_samplers_refuse():
     # the persistent kernel's loci, a composite
     for data, kind in ((fit, "persistent"), (fit + gtr, "composite")):
         smp = make(data)
-        with pytest.raises(bpp_amd.BpaError, match="BPA_SMP_GENERIC=1"):
+        with pytest.raises(bpp_amd.BpaError, match="implementation = BPA_SAMPLER_GENERIC in the options"):
             smp.set_heredity(np.full(len(data), 0.75))
-        with pytest.raises(bpp_amd.BpaError, match="BPA_SMP_GENERIC=1"):
+        with pytest.raises(bpp_amd.BpaError, match="implementation = BPA_SAMPLER_GENERIC in the options"):
             smp.set_heredity_move(0.5, 4.0, 4.0)
         smp.set_heredity_move(0.0)                                  # nothing asked for
         assert smp.kind() == kind

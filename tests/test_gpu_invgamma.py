@@ -1,6 +1,6 @@
 """Inverse-gamma theta / tau priors (BPP's defaults; bpa_sampler_set_prior_kinds) on the device samplers that have them — the
-generic sampler (uniform windows; the program's moves decided on the device by gsm::gdec_kernel<.., 1> and, BPA_GS_HOSTDEC=1, on
-the host), the big-tree sampler (both move sets) and the one-launch-per-step sampler (BPA_SMP_V1=1: smp::decide,
+generic sampler (uniform windows; the program's moves decided on the device by gsm::gdec_kernel<.., 1> and, host_decisions, on
+the host), the big-tree sampler (both move sets) and the one-launch-per-step sampler (implementation="sweep": smp::decide,
 theta_sum_decide_kernel):
 
  * decision by decision against the C host driver with a00_set_prior_kinds on the same library (tests/invgamma.py: pair_walk);
@@ -35,14 +35,10 @@ def gtr8(n, theta=None):
     return _SETS[n, theta]
 
 
-def pair(eng, data, seed, monkeypatch, env=(), scaling=False):
-    """(host driver, device sampler) on two sets of engine loci; env: switches read when the sampler is made"""
+def pair(eng, data, seed, env={}, scaling=False):
+    """(host driver, device sampler) on two sets of engine loci; env: the sampler's options"""
     host = IG.KindDriver(hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data, scaling), data, seed=seed, scaling=scaling))
-    for e in env:
-        monkeypatch.setenv(*e.split("="))
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data, scaling), data, seed=seed)
-    for e in env:
-        monkeypatch.delenv(e.split("=")[0])
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data, scaling), data, seed=seed, **env)
     return host, dev
 
 
@@ -51,13 +47,13 @@ def moved(dev, stree):
 
 
 # ---------------------------------------------------------------- 5. generic sampler
-@pytest.mark.parametrize("moves,env", [("uniform", ()), ("program", ()), ("program", ("BPA_GS_HOSTDEC=1",))])
-def test_generic_sampler_with_inverse_gamma_priors_equals_host_driver(moves, env, monkeypatch):
+@pytest.mark.parametrize("moves,env", [("uniform", {}), ("program", {}), ("program", dict(host_decisions=True))])
+def test_generic_sampler_with_inverse_gamma_priors_equals_host_driver(moves, env):
     """6 GTR+Gamma4 loci of 8 tips (the 128-VGPR step kernel's path), 60 iterations"""
     stree = synth.species_tree_arrays(4)
     data = gtr8(6)
     eng = bpp_amd.Engine(0)
-    host, dev = pair(eng, data, 37, monkeypatch, env)
+    host, dev = pair(eng, data, 37, env)
     program = moves == "program"
     for drv in (host, dev):
         IG.configure(drv, stree, [SP8]*6, moves, theta_prior=(3.0, 0.004, 0.0004 if program else 0.001),
@@ -70,11 +66,11 @@ def test_generic_sampler_with_inverse_gamma_priors_equals_host_driver(moves, env
 
 # ---------------------------------------------------------------- 6. big-tree sampler
 @pytest.mark.parametrize("moves", ["uniform", "program"])
-def test_big_tree_sampler_with_inverse_gamma_priors_equals_host_driver(moves, monkeypatch):
+def test_big_tree_sampler_with_inverse_gamma_priors_equals_host_driver(moves):
     """3 loci of 17 tips (shapes.case('big-17-30'): 8 species), 40 iterations"""
     c = shapes.case("big-17-30")
     eng = bpp_amd.Engine(0)
-    host, dev = pair(eng, c["data"], 23, monkeypatch)
+    host, dev = pair(eng, c["data"], 23)
     program = moves == "program"
     for drv in (host, dev):
         IG.configure(drv, c["stree"], c["species"], moves, theta_prior=(3.0, 0.004, 0.001), finetune=c["finetune"])
@@ -84,11 +80,11 @@ def test_big_tree_sampler_with_inverse_gamma_priors_equals_host_driver(moves, mo
     dev.close(); host.close(); eng.close()
 
 
-def test_big_tree_sampler_forced_on_8_tip_loci_with_inverse_gamma_priors(monkeypatch):
+def test_big_tree_sampler_forced_on_8_tip_loci_with_inverse_gamma_priors():
     stree = synth.species_tree_arrays(4)
     data = gtr8(6)
     eng = bpp_amd.Engine(0)
-    host, dev = pair(eng, data, 41, monkeypatch, ("BPA_SMP_BIG=1",))
+    host, dev = pair(eng, data, 41, dict(implementation="big"))
     for drv in (host, dev):
         IG.configure(drv, stree, [SP8]*6, "program", theta_prior=(3.0, 0.004, 0.0004), finetune=(0.003, 0.005, 0.0004, 0.05))
     IG.pair_walk(host, dev, 40, 6, 1e-9, True)
@@ -98,12 +94,12 @@ def test_big_tree_sampler_forced_on_8_tip_loci_with_inverse_gamma_priors(monkeyp
 
 
 # ---------------------------------------------------------------- 7. one launch per step
-def test_one_launch_per_step_sampler_with_inverse_gamma_priors_equals_host_driver(monkeypatch):
-    """BPA_SMP_V1=1: 8 JC69 loci of 4 tips, uniform windows, 60 iterations"""
+def test_one_launch_per_step_sampler_with_inverse_gamma_priors_equals_host_driver():
+    """implementation="sweep": 8 JC69 loci of 4 tips, uniform windows, 60 iterations"""
     stree = synth.species_tree_arrays(4)
     data = synth.make_dataset(8, 300, 4, "jc69", 1, seed=47)
     eng = bpp_amd.Engine(0)
-    host, dev = pair(eng, data, 53, monkeypatch, ("BPA_SMP_V1=1",))
+    host, dev = pair(eng, data, 53, dict(implementation="sweep"))
     for drv in (host, dev):
         IG.configure(drv, stree, None, "uniform")
     IG.pair_walk(host, dev, 60, 8, 1e-12, False)
@@ -115,7 +111,7 @@ def test_one_launch_per_step_sampler_with_inverse_gamma_priors_equals_host_drive
 # ---------------------------------------------------------------- 8. prior only
 @pytest.mark.parametrize("moves", ["uniform", "program"])
 @pytest.mark.parametrize("which", ["generic", "big"])
-def test_prior_only_run_on_the_device_leaves_the_inverse_gamma_priors(which, moves, monkeypatch):
+def test_prior_only_run_on_the_device_leaves_the_inverse_gamma_priors(which, moves):
     """usedata = 0; generic: 12 loci of 8 tips, big-tree: 6 of them forced onto it; every move on, 500 + 2 000 x 3 iterations
     (tests/test_gpu_heredity.py, tests/test_gpu_bigsampler_scalars.py): every 1/theta ~ gamma(3, 2 theta_0), 1/tau_root ~
     gamma(3, 2 tau_0) — the host driver's check (tests/test_invgamma_host.py: its scale theta_0 = 0.01, its theta window and why), same step
@@ -125,10 +121,7 @@ def test_prior_only_run_on_the_device_leaves_the_inverse_gamma_priors(which, mov
     data = gtr8(n, PRIOR_THETA)
     eng = bpp_amd.Engine(0)
     eng.set_options(usedata=0, bfbeta=1.0)
-    if which == "big":
-        monkeypatch.setenv("BPA_SMP_BIG", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=17)
-    monkeypatch.delenv("BPA_SMP_BIG", raising=False)
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=17, implementation="big" if which == "big" else None)
     theta_prior, tau_prior = (3.0, 2.0*PRIOR_THETA), (3.0, 2.0*stree[1][-1])
     IG.configure(dev, stree, [SP8]*n, moves, theta_prior=theta_prior + (PRIOR_FT_THETA,), tau_prior=tau_prior, finetune=(0.008, 0.008, 0.002, 0.5))
     dev.initialize()
@@ -144,13 +137,11 @@ def test_prior_only_run_on_the_device_leaves_the_inverse_gamma_priors(which, mov
 
 # ---------------------------------------------------------------- 9. the program's posterior
 @pytest.mark.parametrize("moves", ["uniform", "program"])
-def test_generic_sampler_reproduces_bpp_posterior_under_inverse_gamma_priors(gold, moves, monkeypatch):      # noqa: F811
-    """BPA_SMP_GENERIC=1 (these loci would fit the LDS kernels), 2 000 + 4 000 x 2 iterations, the fixture's bars"""
+def test_generic_sampler_reproduces_bpp_posterior_under_inverse_gamma_priors(gold, moves):      # noqa: F811
+    """implementation="generic" (these loci would fit the LDS kernels), 2 000 + 4 000 x 2 iterations, the fixture's bars"""
     data = dataset(gold)
     eng = bpp_amd.Engine(0)
-    monkeypatch.setenv("BPA_SMP_GENERIC", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=10)
-    monkeypatch.delenv("BPA_SMP_GENERIC")
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=10, implementation="generic")
     setup(dev, gold, moves == "program")
     dev.initialize()
     assert dev.kind() == "generic"
@@ -177,7 +168,7 @@ def test_the_persistent_kernel_refuses_and_runs_on_unchanged():
         smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=2)
         IG.configure(smp, stree, None, "uniform", theta_prior=(2.0, 1000.0, 0.0005), tau_prior=(3.0, 3.0/stree[1][-1]), kinds=None)
         if ask:
-            with pytest.raises(bpp_amd.BpaError, match="the persistent kernel has the gamma priors only: BPA_SMP_GENERIC=1 or BPA_SMP_V1=1 at creation"):
+            with pytest.raises(bpp_amd.BpaError, match="the persistent kernel has the gamma priors only: implementation = BPA_SAMPLER_GENERIC or BPA_SAMPLER_SWEEP in the options at creation"):
                 smp.set_prior_kinds("invgamma", "invgamma")
         smp.initialize()
         smp.iterate(20)
@@ -188,7 +179,7 @@ def test_the_persistent_kernel_refuses_and_runs_on_unchanged():
     eng.close()
 
 
-def test_gamma_gamma_is_the_trajectory_of_a_sampler_that_never_heard_of_the_call(monkeypatch):
+def test_gamma_gamma_is_the_trajectory_of_a_sampler_that_never_heard_of_the_call():
     stree = synth.species_tree_arrays(4)
     data = gtr8(6)
     eng = bpp_amd.Engine(0)
@@ -207,17 +198,14 @@ def test_gamma_gamma_is_the_trajectory_of_a_sampler_that_never_heard_of_the_call
 
 
 @pytest.mark.parametrize("which,moves", [("generic", "uniform"), ("generic", "program"), ("big", "uniform"), ("big", "program")])
-def test_state_invariants_after_inverse_gamma_runs(which, moves, monkeypatch):
+def test_state_invariants_after_inverse_gamma_runs(which, moves):
     """100 iterations under inverse-gamma priors, then tests/invariants.py's recompute of every locus's likelihood, density,
     populations and buffers from (tree, taus, thetas)"""
     stree = synth.species_tree_arrays(4)
     data = gtr8(6)
     eng = bpp_amd.Engine(0)
-    if which == "big":
-        monkeypatch.setenv("BPA_SMP_BIG", "1")
     loci = tape.make_engine_loci(eng, data)
-    smp = bpp_amd.Sampler(eng, loci, data, seed=19)
-    monkeypatch.delenv("BPA_SMP_BIG", raising=False)
+    smp = bpp_amd.Sampler(eng, loci, data, seed=19, implementation="big" if which == "big" else None)
     program = moves == "program"
     IG.configure(smp, stree, [SP8]*6, moves, theta_prior=(3.0, 0.004, 0.0004 if program else 0.001),
                  finetune=(0.003, 0.005, 0.0004, 0.05) if program else (0.003, 0.005, 0.0008, 0.2))

@@ -9,50 +9,46 @@ import bpp_amd
 from bpp_amd import synth
 import tape
 import locusrates as LR
+import shapes
 
 pytestmark = pytest.mark.gpu
 
 
-def _pair(c, seed, monkeypatch, generic=False, env=None):
+def _pair(c, seed, generic=False, **options):
     """(engine, engine loci of the device sampler, host driver, device sampler) on case c's data"""
-    if env:
-        monkeypatch.setenv(*env.split("="))
     eng = bpp_amd.Engine(0)
     data = c["data"]
     loci_a = tape.make_engine_loci(eng, data)
     loci_b = tape.make_engine_loci(eng, data)
     host = LR.hip_driver(eng, loci_a, data, seed=seed)
-    if generic:
-        monkeypatch.setenv("BPA_SMP_GENERIC", "1")
-    dev = bpp_amd.Sampler(eng, loci_b, data, seed=seed)
-    monkeypatch.delenv("BPA_SMP_GENERIC", raising=False)
+    dev = bpp_amd.Sampler(eng, loci_b, data, seed=seed, implementation="generic" if generic else None, **options)
     return eng, loci_b, host, dev
 
 
-# case, moves, iterations, environment, mu_bar prior (None: fixed), what must hold besides the trajectory
+# case, moves, iterations, options, mu_bar prior (None: fixed), what must hold besides the trajectory
 TRAJECTORIES = [
     ("a", "uniform", 5, None, (10.0, 10.0)),                       # 70 loci: two workgroups of gstep_kernel; the chain launch
-    ("a", "uniform", 5, "BPA_GS_CHAIN=0", (10.0, 10.0)),           # ... and a launch per step
+    ("a", "uniform", 5, dict(chain=False), (10.0, 10.0)),           # ... and a launch per step
     ("a", "program", 3, None, (10.0, 10.0)),                       # BPP's kernel, MUBAR decided on the device from GDecState::z
-    ("a", "program", 3, "BPA_GS_HOSTDEC=1", (10.0, 10.0)),         # ... and on the host
+    ("a", "program", 3, dict(host_decisions=True), (10.0, 10.0)),         # ... and on the host
     ("b", "uniform", 5, None, (10.0, 10.0)),                       # two part-batches, fuse_pm, MUI after the alpha step
     ("b", "program", 3, None, (10.0, 10.0)),
-    ("b", "program", 3, "BPA_GS_HOSTDEC=1", (10.0, 10.0)),
+    ("b", "program", 3, dict(host_decisions=True), (10.0, 10.0)),
     ("c", "uniform", 5, None, None),                               # 16 tips: 32-lane groups; mu_bar fixed
     ("d", "uniform", 5, None, (10.0, 10.0)),                       # 20-state records, parts of the loci
     # mu_bar fixed and ALL iterations in one call: the rate step that ends an iteration is settled inside the next iteration's
     # first proposal launch (LR.walk: one_call) — the lane groups' settle of mode 9, 16 and 32 lanes, fuse_pm on, both
     # proposal kernels, the 20-state records
-    ("b", "uniform", 5, "ONE_CALL", None),
-    ("b", "program", 3, "ONE_CALL", None),
-    ("c", "uniform", 5, "ONE_CALL", None),
-    ("d", "uniform", 5, "ONE_CALL", None),
-    ("a", "uniform", 5, "ONE_CALL+BPA_GS_CHAIN=0", None),
+    ("b", "uniform", 5, dict(one_call=True), None),
+    ("b", "program", 3, dict(one_call=True), None),
+    ("c", "uniform", 5, dict(one_call=True), None),
+    ("d", "uniform", 5, dict(one_call=True), None),
+    ("a", "uniform", 5, dict(one_call=True, chain=False), None),
 ]
 
 
-@pytest.mark.parametrize("name,moves,iters,env,mubar_prior", TRAJECTORIES)
-def test_device_sampler_with_rate_moves_equals_host_driver(name, moves, iters, env, mubar_prior, monkeypatch):
+@pytest.mark.parametrize("name,moves,iters,env,mubar_prior", TRAJECTORIES, ids=shapes.option_id)
+def test_device_sampler_with_rate_moves_equals_host_driver(name, moves, iters, env, mubar_prior):
     """rates spread over 0.5 .. 2, MUI + MUBAR on: same decisions, counters, trees and buffer indices as the host driver's
     mui_step / mubar_step; ages, taus, thetas to walk's tolerances (1e-12 uniform, 1e-9 with the program's moves: libm on both
     sides of a Bactrian-Laplace window), rates and their mean to 1e-11 (exp / log of device libm against glibc: the
@@ -60,9 +56,9 @@ def test_device_sampler_with_rate_moves_equals_host_driver(name, moves, iters, e
     c = LR.case(name)
     n = len(c["data"])
     subst = name == "b"
-    one_call = bool(env) and env.startswith("ONE_CALL")
-    env = (env[9:] or None) if one_call else env
-    eng, loci, host, dev = _pair(c, 29, monkeypatch, generic=name == "a", env=env)
+    env = dict(env or {})
+    one_call = env.pop("one_call", False)
+    eng, loci, host, dev = _pair(c, 29, generic=name == "a", **env)
     rates = LR.spread_rates(n, 0.5, 2.0)
     for drv, is_host in ((host, True), (dev, False)):
         LR.configure(drv, c, moves, is_host, subst=subst, mubar_prior=mubar_prior, rates=rates)
@@ -163,7 +159,7 @@ def test_rates_of_one_change_nothing_on_the_device():
     eng.close()
 
 
-def test_what_the_device_samplers_refuse(monkeypatch):
+def test_what_the_device_samplers_refuse():
     eng = bpp_amd.Engine(0)
     parent, tau0, thetas = synth.species_tree_arrays(8)
     fit = synth.make_dataset(20, 300, 8, "jc69", 1, seed=5)
@@ -178,9 +174,9 @@ def test_what_the_device_samplers_refuse(monkeypatch):
     # the persistent kernel's loci, a composite
     for data, kind in ((fit, "persistent"), (fit + gtr, "composite")):
         smp = make(data)
-        with pytest.raises(bpp_amd.BpaError, match="BPA_SMP_GENERIC=1"):
+        with pytest.raises(bpp_amd.BpaError, match="implementation = BPA_SAMPLER_GENERIC in the options"):
             smp.set_locus_rates(np.full(len(data), 1.5))
-        with pytest.raises(bpp_amd.BpaError, match="BPA_SMP_GENERIC=1"):
+        with pytest.raises(bpp_amd.BpaError, match="implementation = BPA_SAMPLER_GENERIC in the options"):
             smp.set_locusrate_moves(0.5, 0.0, 5.0)
         smp.set_locusrate_moves(0.0, 0.0, 0.0)                      # nothing asked for
         assert smp.kind() == kind

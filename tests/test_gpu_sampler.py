@@ -3,7 +3,6 @@ driver on libbpp_amd.so with the same seed — which in turn equals the host dri
 reference (test_gpu_host_driver.py).  Same proposals (integer random streams), same
 accept/reject history, same trees; ages and log-likelihoods to ~1e-12 (device exp/log vs glibc
 in the root-age and mixing multipliers)."""
-import os
 
 import numpy as np
 import pytest
@@ -64,12 +63,8 @@ def test_sampler_equals_host_driver(taxa, nloci, iters):
     host.close(); dev.close(); eng.close()
 
 
-def _sampler(eng, data, taxa, seed, v1, monkeypatch):
-    if v1:
-        monkeypatch.setenv("BPA_SMP_V1", "1")
-    else:
-        monkeypatch.delenv("BPA_SMP_V1", raising=False)
-    smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=seed)
+def _sampler(eng, data, taxa, seed, v1):
+    smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=seed, implementation="sweep" if v1 else None)
     parent, tau0, thetas = synth.species_tree_arrays(taxa)
     smp.set_species_tree(parent, tau0, thetas)
     smp.set_tau_prior(3.0, 3.0 / tau0[-1])
@@ -80,14 +75,14 @@ def _sampler(eng, data, taxa, seed, v1, monkeypatch):
 
 
 @pytest.mark.parametrize("taxa,nloci,iters", [(4, 3000, 12), (8, 150, 6)])
-def test_persistent_kernel_equals_one_launch_per_step(taxa, nloci, iters, monkeypatch):
+def test_persistent_kernel_equals_one_launch_per_step(taxa, nloci, iters):
     """the persistent iteration kernel (csrc/sweep2.hpp: state in LDS for the whole launch, all-loci decisions from
-    fixed-point device accumulators over several workgroups) and the one-launch-per-step path (BPA_SMP_V1=1) walk the
+    fixed-point device accumulators over several workgroups) and the one-launch-per-step path (implementation="sweep") walk the
     same trajectory: every tree, every tau and theta, bit for bit — also when one call runs several iterations"""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 600, taxa, "jc69", 1, seed=5)
-    new = _sampler(eng, data, taxa, 11, False, monkeypatch)
-    old = _sampler(eng, data, taxa, 11, True, monkeypatch)
+    new = _sampler(eng, data, taxa, 11, False)
+    old = _sampler(eng, data, taxa, 11, True)
     for it in range(iters):
         n = 1 if it % 3 else 4
         new.iterate(n); old.iterate(n)
@@ -106,7 +101,7 @@ def test_persistent_kernel_equals_one_launch_per_step(taxa, nloci, iters, monkey
     new.close(); old.close(); eng.close()
 
 
-def test_sweeps_of_the_persistent_kernel_between_one_launch_all_loci_steps(monkeypatch):
+def test_sweeps_of_the_persistent_kernel_between_one_launch_all_loci_steps():
     """several ranks: an all-reduce callback is installed, so the all-loci steps run one launch each (their sums go
     through the callback) while the per-locus sweep is the persistent kernel's — which then applies the pending decision
     of the previous iteration's last step while it loads (rejected: the trees come from the pre-step snapshot).  One rank
@@ -115,11 +110,7 @@ def test_sweeps_of_the_persistent_kernel_between_one_launch_all_loci_steps(monke
     data = synth.make_dataset(400, 400, 4, "jc69", 1, seed=3)
 
     def make(v1):
-        if v1:
-            monkeypatch.setenv("BPA_SMP_V1", "1")
-        else:
-            monkeypatch.delenv("BPA_SMP_V1", raising=False)
-        smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=7)
+        smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=7, implementation="sweep" if v1 else None)
         smp.set_allreduce(lambda p, n, st: True, None, 0)          # (the sums stay in the sampler's own device memory)
         parent, tau0, thetas = synth.species_tree_arrays(4)
         smp.set_species_tree(parent, tau0, thetas)
@@ -230,7 +221,7 @@ def test_sampler_rejects_unsupported_loci(engine):
     """GTR+G loci are the generic sampler's (tests/test_gpu_gsampler.py), loci with scale buffers the big-tree sampler's
     (tests/test_gpu_bigsampler.py); amino-acid loci with scalers are refused loudly; a mix of one- and several-category loci —
     refused until round 4 — is dealt to a part per kind (csrc/composite.hpp; trajectory: tests/test_gpu_gsampler.py), and with
-    BPA_SMP_NO_COMPOSITE=1 refused as before"""
+    composite=False refused as before"""
     data = synth.make_dataset(2, 200, 8, "gtr", 4, seed=1)
     loci = tape.make_engine_loci(engine, data, True)                  # with scale buffers
     smp = bpp_amd.Sampler(engine, loci, data)
@@ -251,15 +242,11 @@ def test_sampler_rejects_unsupported_loci(engine):
     with pytest.raises(bpp_amd.BpaError, match="several kinds"):
         smp.set_proposal_kernel(1)
     smp.close()
-    os.environ["BPA_SMP_NO_COMPOSITE"] = "1"
-    try:
-        with pytest.raises(bpp_amd.BpaError, match="all be JC69"):
-            bpp_amd.Sampler(engine, tape.make_engine_loci(engine, mixed), mixed)
-    finally:
-        os.environ.pop("BPA_SMP_NO_COMPOSITE", None)
+    with pytest.raises(bpp_amd.BpaError, match="all be JC69"):
+        bpp_amd.Sampler(engine, tape.make_engine_loci(engine, mixed), mixed, composite=False)
 
 
-def test_native_rccl_callback(monkeypatch):
+def test_native_rccl_callback():
     """the several-GPU exchange as native code (include/bpp_amd_rccl.h, libbpp_amd_rccl.so): ncclAllReduce on the
     engine's stream behind bpa_allreduce_fn — no Python inside bpa_sampler_iterate.  A one-rank communicator (two ranks
     cannot share the test box's single GPU under RCCL; the two-process tests use gloo): the sums come back unchanged, so
@@ -269,11 +256,7 @@ def test_native_rccl_callback(monkeypatch):
     x = bpp_amd.RcclExchange(bpp_amd.RcclExchange.unique_id(), 1, 0, 0)
 
     def make(v1, native):
-        if v1:
-            monkeypatch.setenv("BPA_SMP_V1", "1")
-        else:
-            monkeypatch.delenv("BPA_SMP_V1", raising=False)
-        smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=5)
+        smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=5, implementation="sweep" if v1 else None)
         if native:
             smp.set_allreduce_native(x, None, 0)
         parent, tau0, thetas = synth.species_tree_arrays(4)
@@ -380,23 +363,19 @@ def test_persistent_kernel_at_edge_sizes(taxa, program):
 
 
 @pytest.mark.parametrize("moves", ["uniform", "bpp", "program"])
-@pytest.mark.parametrize("inject", ["2", "3,w"])
-def test_a_launch_that_gives_up_is_run_again_on_the_same_random_numbers(moves, inject, monkeypatch):
+@pytest.mark.parametrize("inject", [2, (3, True)], ids=["2", "3,w"])
+def test_a_launch_that_gives_up_is_run_again_on_the_same_random_numbers(moves, inject):
     """A persistent launch whose workgroups are not all resident together (a shared device) gives up and leaves the loci as it
     found them; the launches queued behind it give up at once and the iterations run again, in order, from the state and the
     global stream the first of them started from: the chain is the one a run without the time-out walks, to the bit.
-    BPA_SMP_INJECT=k makes the k-th launch give up at its first wait (",w": workgroup 0 alone, the others then meet the real
+    inject=k makes the k-th launch give up at its first wait ((k, True): workgroup 0 alone, the others then meet the real
     0.5 s time-out at the next exchange and workgroup 0's copy of the decision is thrown away with theirs)."""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(1100, 400, 4, "jc69", 1, seed=29)
     parent, tau0, thetas = synth.species_tree_arrays(4)
 
-    def run(env):
-        if env:
-            monkeypatch.setenv("BPA_SMP_INJECT", env)
-        else:
-            monkeypatch.delenv("BPA_SMP_INJECT", raising=False)
-        smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=31)
+    def run(inject):
+        smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=31, inject=inject)
         if moves != "uniform":
             smp.set_proposal_kernel(1)
         if moves == "program":

@@ -31,21 +31,21 @@ pytestmark = pytest.mark.gpu
 MOVES = ["uniform", "program"]
 
 
-def sampler(eng, c, moves, seed, scaling=False):
+def sampler(eng, c, moves, seed, scaling=False, **options):
     loci = tape.make_engine_loci(eng, c["data"], scaling)
-    dev = bpp_amd.Sampler(eng, loci, c["data"], seed=seed)
+    dev = bpp_amd.Sampler(eng, loci, c["data"], seed=seed, **options)
     shapes.configure(dev, c, moves)
     return dev, loci
 
 
-def walk_and_grow(name, moves, chunks=(1, 7, 200), scaling=False, tag=""):
+def walk_and_grow(name, moves, chunks=(1, 7, 200), scaling=False, tag="", **options):
     """-> the sampler after grow (open, with its engine: the caller closes both)"""
     c = shapes.case(name)
     n = len(c["data"])
     eng = bpp_amd.Engine(0)
     host = hostdrv.hip_driver(eng, tape.make_engine_loci(eng, c["data"], scaling), c["data"], seed=29, scaling=scaling)
     shapes.configure(host, c, moves, host=True)
-    dev, _ = sampler(eng, c, moves, 29, scaling)
+    dev, _ = sampler(eng, c, moves, 29, scaling, **options)
     # (the program's moves go through libm's log / sqrt / lgamma on both sides: the tolerance the existing walks give them)
     walk(host, dev, 4, n, **(dict(tol=1e-9) if moves == "program" else {}))
     assert dev.kind() == c["kind"]
@@ -54,7 +54,7 @@ def walk_and_grow(name, moves, chunks=(1, 7, 200), scaling=False, tag=""):
             (fh, qh, ah), (fd, qd, ad) = host.get_subst_model(i), dev.get_subst_model(i)
             assert np.allclose(fd, fh, rtol=1e-11, atol=0) and np.allclose(qd, qh, rtol=1e-11, atol=0) and abs(ad - ah) <= 1e-11 * abs(ah), i
     host.close(); dev.close()
-    dev, loci = sampler(eng, c, moves, 31, scaling)
+    dev, loci = sampler(eng, c, moves, 31, scaling, **options)
     dev.initialize()
     assert dev.kind() == c["kind"]
     grow(f"limits-{name}-{moves}{tag}", dev, chunks, c["stree"][1], c["stree"][2], data=c["data"], species_parent=c["stree"][0], loci=loci,
@@ -90,18 +90,15 @@ def test_persistent_kernel_with_loci_of_2_to_8_tips_in_one_sampler(moves):
 
 # ------------------------------------------------------------------ c: one launch per step
 @pytest.mark.parametrize("name", ["persistent-4", "persistent-8", "persistent-mixed-tips"])
-def test_persistent_kernel_equals_one_launch_per_step_at_the_limits(name, monkeypatch):
+def test_persistent_kernel_equals_one_launch_per_step_at_the_limits(name):
     """what tests/test_gpu_sampler.py::test_persistent_kernel_equals_one_launch_per_step asserts, on the shaped lists: trees,
     taus, thetas and counters bit for bit over 6 iterations in chunks of 1 and 4"""
     c = shapes.case(name)
     eng = bpp_amd.Engine(0)
-    monkeypatch.delenv("BPA_SMP_V1", raising=False)
     new, _ = sampler(eng, c, "uniform", 11)
     new.initialize()
-    monkeypatch.setenv("BPA_SMP_V1", "1")
-    old, _ = sampler(eng, c, "uniform", 11)
+    old, _ = sampler(eng, c, "uniform", 11, implementation="sweep")
     old.initialize()
-    monkeypatch.delenv("BPA_SMP_V1")
     assert new.kind() == "persistent" and old.kind() == "sweep"
     for it, n in enumerate((1, 4, 1)):
         new.iterate(n); old.iterate(n)
@@ -137,19 +134,18 @@ def test_64_and_65_pattern_loci_in_turns_with_gtr_loci_make_a_composite():
 
 
 # ------------------------------------------------------------------ e: the generic sampler
-@pytest.mark.parametrize("chain", ["0", "1"])
+@pytest.mark.parametrize("chain", [0, 1])
 @pytest.mark.parametrize("moves", MOVES)
 @pytest.mark.parametrize("name", ["generic-16-jc", "generic-16-gtr-g4", "generic-16-gtr-g3", "generic-16-gtr-g8", "generic-12-and-16"])
-def test_generic_sampler_at_its_limits(name, moves, chain, monkeypatch):
+def test_generic_sampler_at_its_limits(name, moves, chain):
     """16 tips; JC69 at 1, 64, 200 and 255 patterns; GTR+Gamma4 at 63 patterns (252 lanes) with the parameter moves; GTR with 3
     categories at 85 (255 lanes), with 8 at 31 (248); 12 and 16 tips in one sampler.  The per-locus steps as a launch each
-    (BPA_GS_CHAIN=0) and as one launch (1)"""
-    monkeypatch.setenv("BPA_GS_CHAIN", chain)
+    (chain=0) and as one launch (1)"""
     c = shapes.case(name)
     lanes = max(len(d["weights"]) * d["rate_cats"] for d in c["data"])
     assert max(len(s) for s in c["species"]) == 16 and lanes == {"generic-16-jc": 255, "generic-16-gtr-g4": 252, "generic-16-gtr-g3": 255,
                                                                  "generic-16-gtr-g8": 248, "generic-12-and-16": 100}[name]
-    dev, eng = walk_and_grow(name, moves, tag=f"-chain{chain}")
+    dev, eng = walk_and_grow(name, moves, tag=f"-chain{chain}", chain=chain)
     if c["subst"]:
         assert any(dev.get_subst_model(i)[2] != 0.5 for i in range(len(c["data"])))
     dev.close(); eng.close()

@@ -50,7 +50,7 @@ those that pass by the 5e-16 absolute bar instead; logpr was 0.0 in every case, 
   (at branch lengths of 1e-10 .. 1e-8 expm1(x) is x on both sides: every P-matrix, and with it every lnL, had the oracle's bits; the
   batched plans, the tapes — 220 steps per locus, JC69 and GTR+G4 — and the host driver's 5 iterations of that file were 0.0 from the
   oracle / the reference as well)
-  (generic: BPA_GS_CHAIN=0 and 1 gave the same figures; big: with and without scale buffers gave the same figures.  On the loci of
+  (generic: chain=0 and 1 gave the same figures; big: with and without scale buffers gave the same figures.  On the loci of
   tests/shapes.py no scale counter of the oracle's recompute is non-zero at 17 or 64 tips — those cases compare zeros; the counters
   that are non-zero are the four cases above and the golden loci 9-11 / K1 vectors of tests/test_gpu_parity.py)
 
@@ -91,11 +91,11 @@ def grow(case, dev, chunks, tau0, thetas0, **kw):
 
 
 def make(eng, data, stree, seed, moves, species=None, prior=(2.0, 1000.0, 0.0004), finetune=(0.003, 0.004, 0.0004, 0.1), tau_prior=None,
-         loci=None, slide=0.3):
+         loci=None, slide=0.3, **options):
     """moves: 'uniform' (the library's own windows), 'bpp' (BPP's kernel), 'program' (BPP's kernel and the program's moves)"""
     parent, tau0, thetas = stree
     loci = tape.make_engine_loci(eng, data) if loci is None else loci
-    dev = bpp_amd.Sampler(eng, loci, data, seed=seed)
+    dev = bpp_amd.Sampler(eng, loci, data, seed=seed, **options)
     if moves != "uniform":
         dev.set_proposal_kernel(1)
     if moves == "program":
@@ -165,14 +165,12 @@ def test_several_sequences_per_species(program):
     dev.close(); eng.close()
 
 
-def test_one_launch_per_step(monkeypatch):
-    monkeypatch.setenv("BPA_SMP_V1", "1")
+def test_one_launch_per_step():
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(300, 400, 4, "jc69", 1, seed=17)
     stree = synth.species_tree_arrays(4)
-    dev, loci = make(eng, data, stree, 23, "uniform", prior=(2.0, 1000.0, 0.001), finetune=(0.003, 0.005, 0.0008, 0.2))
+    dev, loci = make(eng, data, stree, 23, "uniform", prior=(2.0, 1000.0, 0.001), finetune=(0.003, 0.005, 0.0008, 0.2), implementation="sweep")
     dev.initialize()
-    monkeypatch.delenv("BPA_SMP_V1")
     assert dev.kind() == "sweep"
     grow("sweep", dev, (5, 200), stree[1], stree[2], data=data, species_parent=stree[0], loci=loci)
     dev.close(); eng.close()
@@ -202,16 +200,14 @@ def test_generic_sampler_gtr_gamma_with_parameter_moves(nloci, chunks):
     dev.close(); eng.close()
 
 
-@pytest.mark.parametrize("chain", ["0", "1"])
-def test_generic_sampler_forced_on_jc69_loci(chain, monkeypatch):
-    """the per-locus steps as a launch each (BPA_GS_CHAIN=0) and as ONE launch (1)"""
-    monkeypatch.setenv("BPA_GS_CHAIN", chain)
-    monkeypatch.setenv("BPA_SMP_GENERIC", "1")
+@pytest.mark.parametrize("chain", [0, 1])
+def test_generic_sampler_forced_on_jc69_loci(chain):
+    """the per-locus steps as a launch each (chain=0) and as ONE launch (1)"""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(40, 300, 8, "jc69", 1, seed=19)
     stree = synth.species_tree_arrays(8)
-    dev, loci = make(eng, data, stree, 29, "uniform", prior=(2.0, 1000.0, 0.001), finetune=(0.003, 0.005, 0.0008, 0.2))
-    monkeypatch.delenv("BPA_SMP_GENERIC")
+    dev, loci = make(eng, data, stree, 29, "uniform", prior=(2.0, 1000.0, 0.001), finetune=(0.003, 0.005, 0.0008, 0.2),
+                     implementation="generic", chain=chain)
     dev.initialize()
     assert dev.kind() == "generic"
     grow(f"generic-jc-chain{chain}", dev, (3, 200), stree[1], stree[2], data=data, species_parent=stree[0], loci=loci)

@@ -3,7 +3,7 @@ schedule: bpa_sweep_schedule).  A workgroup with five waves of loci has two of t
 step of its own set and one of each set of the three waves that have a SIMD to themselves, and finishes the last of them; each
 of the three finishes the set the younger wave held before.  Who holds a set must not show in any result: the device against the C host driver on the same seed, and the device against itself on the identity schedule.
 
-BPA_SMP_DBG bits: 4096 deals densely (as few workgroups as hold the waves, so a few dozen loci run as five, six or seven
+the sampler's debug bits: 4096 deals densely (as few workgroups as hold the waves, so a few dozen loci run as five, six or seven
 waves in one workgroup), 8192 keeps the identity schedule, 16 prints workgroup 0's counters — among them whether its sets
 changed waves.
 
@@ -47,9 +47,8 @@ def _setup(drv, taxa, program=True, bpp=True):
     drv.initialize()
 
 
-def _device(eng, data, taxa, monkeypatch, dbg, **kw):
-    monkeypatch.setenv("BPA_SMP_DBG", str(dbg))           # (read when the sampler is created)
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=5)
+def _device(eng, data, taxa, dbg, options={}, **kw):
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=5, debug=dbg, **options)
     _setup(dev, taxa, **kw)
     assert dev.kind() == "persistent"
     return dev
@@ -76,7 +75,7 @@ def _dump(dev, nloci, path):
 
 
 @pytest.mark.parametrize("nloci", [33, 40, 41, 56, 80])
-def test_sets_change_waves_and_nothing_shows(nloci, monkeypatch, tmp_path, capfd):
+def test_sets_change_waves_and_nothing_shows(nloci, tmp_path, capfd):
     """BPP's kernel and the program's moves, 10 iterations as launches of 1, 1, 1 and 7: after every call the host driver's
     counts and Gibbs counters, at the end its taus, thetas and every tree; and every array a caller receives equal, to the
     bit, to a device run on the identity schedule"""
@@ -84,7 +83,7 @@ def test_sets_change_waves_and_nothing_shows(nloci, monkeypatch, tmp_path, capfd
     data = synth.make_dataset(nloci, 300, 4, "jc69", 1, seed=100 + nloci)
     host = hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data), data, seed=5)
     _setup(host, 4)
-    dev = _device(eng, data, 4, monkeypatch, DENSE | COUNTERS)
+    dev = _device(eng, data, 4, DENSE | COUNTERS)
     _against_host(dev, host, nloci)
     err = capfd.readouterr().err
     five = nloci in (33, 40, 80)
@@ -95,7 +94,7 @@ def test_sets_change_waves_and_nothing_shows(nloci, monkeypatch, tmp_path, capfd
         assert line.count("*") == 5, line
     got = _dump(dev, nloci, tmp_path / "handover")
     dev.close()
-    ref = _device(eng, data, 4, monkeypatch, DENSE | IDENTITY)
+    ref = _device(eng, data, 4, DENSE | IDENTITY)
     for chunk in CHUNKS:
         ref.iterate(chunk)
     want = _dump(ref, nloci, tmp_path / "identity")
@@ -105,32 +104,32 @@ def test_sets_change_waves_and_nothing_shows(nloci, monkeypatch, tmp_path, capfd
     host.close(); ref.close(); eng.close()
 
 
-def test_uniform_windows_keep_the_identity_schedule(monkeypatch, capfd):
+def test_uniform_windows_keep_the_identity_schedule(capfd):
     """iter_kernel<4, false>: no control wave, every wave keeps its set"""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(40, 300, 4, "jc69", 1, seed=140)
     host = hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data), data, seed=5)
     _setup(host, 4, program=False, bpp=False)
-    dev = _device(eng, data, 4, monkeypatch, DENSE | COUNTERS, program=False, bpp=False)
+    dev = _device(eng, data, 4, DENSE | COUNTERS, program=False, bpp=False)
     _against_host(dev, host, 40, gibbs=False)
     assert "sets change waves: no" in capfd.readouterr().err
     host.close(); dev.close(); eng.close()
 
 
-def test_eight_taxa_keep_the_identity_schedule(monkeypatch, capfd):
+def test_eight_taxa_keep_the_identity_schedule(capfd):
     """iter_kernel<8, true, true>: 16 lanes a locus, three waves of loci a workgroup"""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(20, 300, 8, "jc69", 1, seed=120)
     host = hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data), data, seed=5)
     _setup(host, 8)
-    dev = _device(eng, data, 8, monkeypatch, DENSE | COUNTERS)
+    dev = _device(eng, data, 8, DENSE | COUNTERS)
     _against_host(dev, host, 20)
     assert "sets change waves: no" in capfd.readouterr().err
     host.close(); dev.close(); eng.close()
 
 
-def test_a_launch_that_gives_up_between_hand_overs_is_run_again(monkeypatch, tmp_path):
-    """BPA_SMP_INJECT=2: the second launch gives up at its first exchange — the sets have changed waves in its sweep by then —
+def test_a_launch_that_gives_up_between_hand_overs_is_run_again(tmp_path):
+    """inject=2: the second launch gives up at its first exchange — the sets have changed waves in its sweep by then —
     and stores nothing; the iterations run again from the trees, the streams and the holders the first launch left in HBM.  The
     chain is the host driver's, and to the bit that of a device run without the time-out."""
     eng = bpp_amd.Engine(0)
@@ -138,13 +137,11 @@ def test_a_launch_that_gives_up_between_hand_overs_is_run_again(monkeypatch, tmp
     data = synth.make_dataset(nloci, 300, 4, "jc69", 1, seed=140)
     host = hostdrv.hip_driver(eng, tape.make_engine_loci(eng, data), data, seed=5)
     _setup(host, 4)
-    monkeypatch.setenv("BPA_SMP_INJECT", "2")
-    dev = _device(eng, data, 4, monkeypatch, DENSE)
+    dev = _device(eng, data, 4, DENSE, dict(inject=2))
     _against_host(dev, host, nloci)
     got = _dump(dev, nloci, tmp_path / "inject")
     dev.close()
-    monkeypatch.delenv("BPA_SMP_INJECT")
-    ref = _device(eng, data, 4, monkeypatch, DENSE)
+    ref = _device(eng, data, 4, DENSE)
     for chunk in CHUNKS:
         ref.iterate(chunk)
     want = _dump(ref, nloci, tmp_path / "plain")

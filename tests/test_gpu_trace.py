@@ -17,7 +17,7 @@ from tracereplay import replay_sum, replay_parts, any_order_bound
 
 pytestmark = pytest.mark.gpu
 
-# (set, moves, how): how = "v1" one launch per step (BPA_SMP_V1=1), "allreduce" a callback installed (the hybrid form)
+# (set, moves, how): how = "v1" one launch per step (implementation="sweep"), "allreduce" a callback installed (the hybrid form)
 CASES = [("persistent-4", "uniform", None), ("persistent-4", "program", None), ("persistent-mixed-tips", "program", None),
          ("persistent-4", "uniform", "v1"), ("persistent-4", "uniform", "allreduce"), ("handover-65", "program", None),
          ("generic-16-gtr-g4", "program", None), ("composite-64-65", "uniform", None), ("big-17-30", "program", None)]
@@ -25,8 +25,8 @@ KIND = {None: None, "v1": "sweep", "allreduce": "hybrid"}
 TOTAL, FIRST = 30, 25
 
 
-def make(eng, c, moves, how=None, seed=31):
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, c["data"]), c["data"], seed=seed)
+def make(eng, c, moves, how=None, seed=31, **options):
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, c["data"]), c["data"], seed=seed, implementation="sweep" if how == "v1" else None, **options)
     shapes.configure(dev, c, moves)
     if how == "allreduce":
         dev.set_allreduce(lambda p, n, st: 1, 0, 0)
@@ -74,13 +74,9 @@ def same_state(a, b):
 
 @pytest.mark.parametrize("every", [1, 3])
 @pytest.mark.parametrize("name,moves,how", CASES, ids=[f"{n}-{m}" + (f"-{h}" if h else "") for n, m, h in CASES])
-def test_rows_equal_stop_and_look_and_tracing_is_neutral(name, moves, how, every, monkeypatch):
+def test_rows_equal_stop_and_look_and_tracing_is_neutral(name, moves, how, every):
     c = shapes.case(name)
     n = len(c["data"])
-    if how == "v1":
-        monkeypatch.setenv("BPA_SMP_V1", "1")
-    else:
-        monkeypatch.delenv("BPA_SMP_V1", raising=False)
     eng = bpp_amd.Engine(0)
     A, B = twins(eng, c, moves, how)
     assert A.kind() == B.kind() == (KIND[how] or c["kind"])
@@ -113,9 +109,9 @@ def test_rows_equal_stop_and_look_and_tracing_is_neutral(name, moves, how, every
     A.close(); B.close(); eng.close()
 
 
-def _program4(eng, every, capacity, seed=31):
+def _program4(eng, every, capacity, seed=31, **options):
     c = shapes.case("persistent-4")
-    dev = make(eng, c, "program", seed=seed)
+    dev = make(eng, c, "program", seed=seed, **options)
     dev.initialize()
     assert dev.kind() == "persistent"
     if every is not None:
@@ -141,17 +137,14 @@ def test_capacity_and_draining():
     X.close(); Y.close(); eng.close()
 
 
-def test_a_launch_that_gives_up_writes_no_row_and_the_rerun_writes_them_in_order(monkeypatch, capfd):
-    """BPA_SMP_INJECT=2 (as tests/test_gpu_sampler.py uses it): the second persistent launch returns at its first wait and
+def test_a_launch_that_gives_up_writes_no_row_and_the_rerun_writes_them_in_order(capfd):
+    """inject=2 (as tests/test_gpu_sampler.py uses it): the second persistent launch returns at its first wait and
     leaves the loci as it found them; the launches behind it give up at once.  With every = 2 a launch is two iterations, so
     iterate(6) + iterate(4) is five launches, of which four do not run — nor may their rows be written; reading the trace
     runs them again."""
     eng = bpp_amd.Engine(0)
-    monkeypatch.delenv("BPA_SMP_INJECT", raising=False)
     P, c = _program4(eng, 2, 16)
-    monkeypatch.setenv("BPA_SMP_INJECT", "2")
-    Q, _ = _program4(eng, 2, 16)
-    monkeypatch.delenv("BPA_SMP_INJECT")
+    Q, _ = _program4(eng, 2, 16, inject=2)
     for dev in (P, Q):
         dev.iterate(6); dev.iterate(4)
     capfd.readouterr()

@@ -8,7 +8,7 @@ tests/test_gtr_posterior.py's bars (0.3 sd on the means, 0.25 sd on the sds).  T
 root's theta: 0.0045 against 0.0062, its sd 0.0014), and both from the posterior without scalars.
 
  * CPU: the C host driver on the REAL reference's locus API (skipped where oracle/_ref is absent);
- * GPU: the generic device-resident sampler (BPA_SMP_GENERIC=1: these loci would fit the LDS kernels) with the uniform kernel
+ * GPU: the generic device-resident sampler (implementation="generic": these loci would fit the LDS kernels) with the uniform kernel
    and with the program's moves.
 """
 import json
@@ -106,14 +106,12 @@ def test_host_driver_with_heredity_reproduces_bpp_posterior(gold, form):
 @pytest.mark.gpu
 @pytest.mark.parametrize("moves", ["uniform", "program"])
 @pytest.mark.parametrize("form", ["estimated", "fixed"])
-def test_device_sampler_with_heredity_reproduces_bpp_posterior(gold, form, moves, monkeypatch):
+def test_device_sampler_with_heredity_reproduces_bpp_posterior(gold, form, moves):
     import bpp_amd
     import tape
     data = dataset(gold)
     eng = bpp_amd.Engine(0)
-    monkeypatch.setenv("BPA_SMP_GENERIC", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=10)
-    monkeypatch.delenv("BPA_SMP_GENERIC")
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=10, implementation="generic")
     if moves == "program":
         dev.set_proposal_kernel(1)
         dev.set_program_moves(True, 0.1)

@@ -70,13 +70,9 @@ def test_host_driver_default_is_gamma_to_the_bit(moves):
 
 
 # ---- what bpa_sampler_set_prior_kinds refuses (a sampler needs a device)
-def _sampler(eng, data, monkeypatch, env=None):
+def _sampler(eng, data, implementation=None):
     import tape
-    if env:
-        monkeypatch.setenv(env, "1")
-    smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=3)
-    if env:
-        monkeypatch.delenv(env)
+    smp = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=3, implementation=implementation)
     parent, tau0, thetas = synth.species_tree_arrays(len(data[0]["seqs"]))
     smp.set_species_tree(parent, tau0, thetas)
     smp.set_tau_prior(3.0, 2.0*tau0[-1])
@@ -85,12 +81,12 @@ def _sampler(eng, data, monkeypatch, env=None):
 
 
 @pytest.mark.gpu
-def test_what_set_prior_kinds_refuses(monkeypatch):
+def test_what_set_prior_kinds_refuses():
     eng = bpp_amd.Engine(0)
     jc4 = synth.make_dataset(8, 300, 4, "jc69", 1, seed=5)
-    way_out = "the persistent kernel has the gamma priors only: BPA_SMP_GENERIC=1 or BPA_SMP_V1=1 at creation"
+    way_out = "the persistent kernel has the gamma priors only: implementation = BPA_SAMPLER_GENERIC or BPA_SAMPLER_SWEEP in the options at creation"
     # loci that fit the persistent kernel get it (alone: BPA_SAMPLER_PERSISTENT; with an all-reduce callback: BPA_SAMPLER_HYBRID)
-    smp = _sampler(eng, jc4, monkeypatch)
+    smp = _sampler(eng, jc4)
     with pytest.raises(bpp_amd.BpaError, match=way_out):
         smp.set_prior_kinds("invgamma", "invgamma")
     with pytest.raises(bpp_amd.BpaError, match=way_out):
@@ -101,8 +97,8 @@ def test_what_set_prior_kinds_refuses(monkeypatch):
     assert smp.kind() == "hybrid"
     smp.close()
     # ... and the message's two ways out are ways out
-    for env, kind in (("BPA_SMP_GENERIC", "generic"), ("BPA_SMP_V1", "sweep")):
-        smp = _sampler(eng, jc4, monkeypatch, env)
+    for kind in ("generic", "sweep"):
+        smp = _sampler(eng, jc4, kind)
         smp.set_prior_kinds("invgamma", "invgamma")
         # a kind other than the two
         for bad in ((2, 0), (0, -1), (1, 7)):
@@ -121,7 +117,7 @@ def test_what_set_prior_kinds_refuses(monkeypatch):
         smp.iterate(2)
         smp.close()
     # a sampler with an all-reduce callback installed, whatever its kind
-    smp = _sampler(eng, jc4, monkeypatch, "BPA_SMP_GENERIC")
+    smp = _sampler(eng, jc4, "generic")
     smp.set_allreduce(lambda p, n, st: True, None, 0)
     with pytest.raises(bpp_amd.BpaError, match="several ranks have the gamma priors only"):
         smp.set_prior_kinds("invgamma", "gamma")

@@ -6,7 +6,7 @@ bars of its seed 1, which is the fixture) against this repo's samplers on the sa
 mu_bar and the log-likelihood within tests/test_gtr_posterior.py's bars (0.3 sd on the means, 0.25 sd on the sds).
 
  * CPU: the C host driver on the REAL reference's locus API (skipped where oracle/_ref is absent);
- * GPU: the generic device-resident sampler (BPA_SMP_GENERIC=1: these loci would fit the LDS kernels) with the uniform kernel
+ * GPU: the generic device-resident sampler (implementation="generic": these loci would fit the LDS kernels) with the uniform kernel
    and with the program's moves.
 """
 import json
@@ -101,14 +101,12 @@ def test_host_driver_with_rate_moves_reproduces_bpp_posterior(gold):
 # The program's moves at their step lengths, same twin: seeds 9, 10, 13 -> worst mean 0.08, 0.06, 0.22 sd.
 @pytest.mark.gpu
 @pytest.mark.parametrize("moves", ["uniform", "program"])
-def test_device_sampler_with_rate_moves_reproduces_bpp_posterior(gold, moves, monkeypatch):
+def test_device_sampler_with_rate_moves_reproduces_bpp_posterior(gold, moves):
     import bpp_amd
     import tape
     data = dataset(gold)
     eng = bpp_amd.Engine(0)
-    monkeypatch.setenv("BPA_SMP_GENERIC", "1")
-    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=10)
-    monkeypatch.delenv("BPA_SMP_GENERIC")
+    dev = bpp_amd.Sampler(eng, tape.make_engine_loci(eng, data), data, seed=10, implementation="generic")
     if moves == "program":
         dev.set_proposal_kernel(1)
         dev.set_program_moves(True, 0.1)
