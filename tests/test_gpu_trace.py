@@ -55,11 +55,23 @@ def parts_of(c):
 
 
 def state(dev, c):
+    """everything a sampler holds that a getter shows; c["subst"], and where a case has them c["rates"], c["hered"] and
+    c["gibbs"] (tests/test_gpu_trace_tails.py), say which features are on: their values and their counters are part of it"""
     s = dev.summary()
-    out = dict(taus=dev.taus(), thetas=dev.thetas(), trees=[dev.tree(i) for i in range(len(c["data"]))],
+    n = len(c["data"])
+    out = dict(taus=dev.taus(), thetas=dev.thetas(), trees=[dev.tree(i) for i in range(n)],
                counts=(s["proposals"], s["accepted"]))
     if c["subst"]:
-        out["subst"] = [tuple(np.asarray(x).tolist() for x in dev.get_subst_model(i)) for i in range(len(c["data"]))]
+        out["subst"] = [tuple(np.asarray(x).tolist() for x in dev.get_subst_model(i)) for i in range(n)]
+    if c.get("rates"):
+        mui, mubar = dev.get_locus_rates()
+        out["rates"] = (mui.tolist(), mubar)
+        out["rate_counts"] = dev.locusrate_counters()
+    if c.get("hered"):
+        out["hered"] = dev.get_heredity().tolist()
+        out["hered_counts"] = dev.heredity_counters()
+    if c.get("gibbs"):
+        out["gibbs"] = tuple(dev.gibbs_counters())
     return out
 
 
@@ -70,6 +82,9 @@ def same_state(a, b):
             assert np.array_equal(x[key], y[key]), (i, key)
     if "subst" in a:
         assert a["subst"] == b["subst"]
+    assert a.keys() == b.keys()
+    for key in a.keys() - {"taus", "thetas", "counts", "trees", "subst"}:
+        assert a[key] == b[key], (key, a[key], b[key])
 
 
 @pytest.mark.parametrize("every", [1, 3])
