@@ -158,6 +158,9 @@ struct WgBase
   Redraw rd[16];
   // the proposal of the species tree of the coming all-loci step, as the control wave publishes it (program-moves kernel)
   struct { int32_t q, mix; double tq_old, tq_lo, tq_hi, tq_new, minf, maxf, lminf, lmaxf, mix_c, mix_lnc; } stepp;
+  // the iteration whose first proposal stands in stepp: the control wave makes it during the sweep before, behind B4 of the MIX
+  // step, and releases this word; the loci waves acquire it ahead of the iteration's first all-loci step (0: the launch prologue's, out since B0)
+  uint32_t stepp_iter, pad_;
 };
 template <int NT> struct WgLDS : WgBase
 {
@@ -172,9 +175,11 @@ template <int NT> struct WgLDS : WgBase
   uint32_t xcoarse_, late_;                      // late_: another workgroup gave up in this launch (read from Args::err before the store)
   uint32_t simd[8];                              // the SIMD every wave of the workgroup runs on (read once at entry)
   uint32_t handoff[8][SCHED_SEGS];               // [role][segment]: (iteration x SCHED_SEGS + segment + 1) << 4 | the set the role parked before that segment
+  unsigned long long twait[8];                   // when a loci wave began to wait for the iteration's first proposal
   unsigned long long b1abs; long long hwait[8], b1last;                    // BPA_SMP_DBG & 16: cycles every wave of workgroup 0 waited at hand-overs; when the last of them had done its sweep
 };
 
+template <bool B> struct BoolC { static constexpr bool value = B; };
 template <int G> __device__ __forceinline__ uint32_t gballot(bool p, uint32_t gbase)
 {
   return (uint32_t)(__ballot(p) >> gbase) & (G >= 32 ? 0xffffffffu : ((1u << (G & 31)) - 1u));
@@ -751,6 +756,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     for (uint32_t i = tid; i < sizeof(Species)/4; i += C::BS) dst[i] = src[i];
     if (tid < 24u) wg.prof[tid] = 0;
     if (tid < 16u) wg.wsweep[tid] = 0;
+    if constexpr (PROG) { if (tid == 0) wg.stepp_iter = 0u; }
     if constexpr (HO)
     {
       if (tid < 8u) { wg.hwait[tid] = 0; wg.roles[tid] = 0xff0u; }
@@ -1078,7 +1084,8 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
           __syncthreads();                                              // B1: every locus's terms are in wg.accfx
           SMP2_TICK(1);
           // a loci wave gave up at a hand-over (it raised the launch's error word): leave as after a timed-out exchange
-          if constexpr (HO) if (wg.abort_) { if (b == 0 && lane == 0) (void)atomicAdd(A.err + 1, (int)A.niter); aborted = true; __syncthreads(); __syncthreads(); break; }
+          // (or at the wait for the iteration's first proposal)
+          if (wg.abort_) { if (b == 0 && lane == 0) (void)atomicAdd(A.err + 1, (int)A.niter); aborted = true; __syncthreads(); __syncthreads(); break; }
           double dummy = 0;
           exchange_begin(base + (mix ? 2 : 5));
           SMP2_TICK(2);
@@ -1150,11 +1157,17 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
           if (mix) SMP2_TICK(6); else SMP2_TICK(5);
           SMP2_TICK(7);
           __syncthreads();                                              // B3: the decision is out, the species tree as it now is
-          // the next step's proposal, while the loci settle this one (after MIX: the next iteration's first TAU and THETA's
-          // choices — unless the launch ends here: the next launch's prologue draws them, the same numbers of the stream)
+          // the next step's proposal, while the loci settle this one
           if (stepq < npop) make_step(stepq + 1);
-          else if (it + 1 < A.niter) { make_step(nsp); theta_choices(); }
           __syncthreads();                                              // B4: the next proposal is out
+          // after MIX: the next iteration's first TAU and THETA's choices, behind B4 — the loci waves are off to their sweep
+          // and want it a whole sweep from now (they wait for stepp_iter); the same numbers of the stream, drawn later.
+          // Unless the launch ends here: the next launch's prologue draws them
+          if (stepq == npop && it + 1 < A.niter)
+          {
+            make_step(nsp); theta_choices();
+            if (lane == 0) __hip_atomic_store(&wg.stepp_iter, it + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
         }
       }
       // a workgroup that became resident late can pass the launch's last exchange after the others gave up there: nobody
@@ -1275,7 +1288,8 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     mynin_new = gl_i - below;
   };
   // the term of population li (density_term of sampler.hpp); tk = ages of the inner nodes
-  auto density_term = [&](const double * tk)
+  // (stat: the statistic T2h alone — no quotient, no term stored)
+  auto density_term = [&](const double * tk, auto stat)
   {
     uint32_t nodes = mynodes;
     const int ncoal = (int)mync_new, nin = mynin_new;
@@ -1299,21 +1313,28 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         T2h += nn*(nn - 1)*(tkk - prev);
         prev = tkk; --nn;
       }
-    double c = 0;
-    if (ncoal) c += ncoal*pl.l2t;
-    if (T2h) c -= T2h/(pl.theta*1.0);
-    S->contrib_new[li] = c; t2h_new = T2h;
+    if constexpr (!decltype(stat)::value)
+    {
+      double c = 0;
+      if (ncoal) c += ncoal*pl.l2t;
+      if (T2h) c -= T2h/(pl.theta*1.0);
+      S->contrib_new[li] = c;
+    }
+    t2h_new = T2h;
   };
   // everything a proposal leaves to do before the decision: density terms, buffer toggles, fresh (a,b), node updates,
   // the ordered sum over the patterns.  Returns the log-likelihood; lp_new = the density.
-  auto evaluate = [&](const Prop & pr, bool with_lnl, double & lp_new) -> double
+  // stat (the all-loci steps of the program's moves: the control wave forms the density change from k_p and the T2h sums, nobody
+  // reads a term or their sum before the iteration's refresh): t2h_new alone, from the counts the caller has made; lp_new stays
+  auto evaluate = [&](const Prop & pr, bool with_lnl, double & lp_new, auto stat) -> double
   {
+    constexpr bool STAT = decltype(stat)::value;
     double tk[NT - 1];
 #pragma unroll
     for (int j = 0; j < NT - 1; ++j) tk[j] = S->time[(tips + j) & (NN - 1)];
     const double myage = S->time[li];
-    density_counts();
-    if ((pr.chain >> li) & 1u) density_term(tk);
+    if constexpr (!STAT) density_counts();
+    if ((pr.chain >> li) & 1u) density_term(tk, stat);
     T.pf ^= pr.brm; T.cf ^= pr.ndm;
     if ((pr.brm >> li) & 1u)
     {
@@ -1387,16 +1408,17 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       lnl = A.bfbeta == 1.0 ? lnl : A.bfbeta == 0.0 ? 0.0 : A.bfbeta*lnl;
     }
     else wsync();
-    double lp = 0;
+    if constexpr (!STAT)
     {
+      double lp = 0;
       // the density terms in population order, loads first (npop < G)
       double v[G];
 #pragma unroll
       for (int p = 0; p < G; ++p) v[p] = p < npop ? (((pr.chain >> p) & 1u) ? S->contrib_new[p] : S->contrib[p]) : 0.0;
 #pragma unroll
       for (int p = 0; p < G; ++p) lp += v[p];
+      lp_new = lp;
     }
-    lp_new = lp;
     return lnl;
   };
   auto commit_density = [&](uint32_t chain)
@@ -1414,7 +1436,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
 #pragma unroll
     for (int j = 0; j < NT - 1; ++j) tk[j] = S->time[(tips + j) & (NN - 1)];
     density_counts();
-    if (li < npop) density_term(tk);
+    if (li < npop) density_term(tk, BoolC<false>{});
     commit_density(allpop);
     wsync();
     if (A.refresh_logpr)
@@ -1606,7 +1628,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       if (ok)
       {
         wsync();
-        lnl = evaluate(pr, true, lp_new);
+        lnl = evaluate(pr, true, lp_new, BoolC<false>{});
         SMP2_TICK(1);
       }
       if (ok)
@@ -1633,6 +1655,33 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       if constexpr (HO) (void)__hip_atomic_fetch_max(&wg.b1abs, (unsigned long long)t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (!A.do_allloci) continue;
+    // ---- the iteration's first proposal of the species tree (wg.stepp): past the launch's first iteration the control wave makes it
+    // during the sweep and releases it under the iteration's number.  The wait — it has had a whole sweep — is bounded as a
+    // hand-over's: the wall clock, the workgroup's abort word, the launch's error word; a wave that gives up raises both words
+    // and goes on without its loci, the control wave finds the abort word behind B1.  (Here, ahead of the steps' variables,
+    // and its start in LDS: inside step_begin, or with the start in a register, <4, true, true, true> spilled 3 - 11 registers)
+    if constexpr (PROG)
+    {
+      if (it && __hip_atomic_load(&wg.stepp_iter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != it)
+      {
+        if (lane == 0) wg.twait[wv & 7u] = wall_clock64();
+        wsync();
+        for (uint32_t rounds = 1;; ++rounds)
+        {
+          __builtin_amdgcn_s_sleep(1);
+          if (__hip_atomic_load(&wg.stepp_iter, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == it) break;
+          bool give_up = __hip_atomic_load(&wg.abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u;
+          if (!give_up && (rounds & 63u) == 0)
+            give_up = wall_clock64() - wg.twait[wv & 7u] > 50000000ull || __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;     // 0.5 s at 100 MHz
+          if (give_up)
+          {
+            if (lane == 0) { __hip_atomic_store(&wg.abort_, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); (void)__hip_atomic_exchange(A.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+            act = false;
+            break;
+          }
+        }
+      }
+    }
 
     // ================= TAU per species divergence, then MIX: one decision each for all loci.  A step in four parts — the
     // proposal of the species tree (step_begin), every locus's share (step_locus: its terms go to the exchange's slots
@@ -1657,7 +1706,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
       rd_mask = 0; lnprior = 0; accept = false; lnacc_theta = 0;
       if constexpr (PROG)
       {
-        // the control wave's proposal of the species tree (wg.stepp, out since the last barrier)
+        // the control wave's proposal of the species tree (wg.stepp, out since the last barrier; an iteration's first: acquired above)
         (void)stepq;
         mix = wg.stepp.mix != 0; q = wg.stepp.q;
         tq_old = wg.stepp.tq_old; tq_lo = wg.stepp.tq_lo; tq_hi = wg.stepp.tq_hi; tq_new = wg.stepp.tq_new;
@@ -1692,7 +1741,9 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         if (pl.parent >= 0) pl.ptau *= mix_c;
       }
     };
-    auto step_locus = [&](int base)
+    // counts (PROG): the step is the iteration's first — the sweep's last proposal may have been rolled back, so the lanes' node
+    // sets and counts are made again; no all-loci step changes a node's population, the later steps keep them
+    auto step_locus = [&](int base, bool counts)
     {
       cf0 = T.cf; pf0 = T.pf;
       tsave = act ? S->time[li] : 0.0;
@@ -1731,7 +1782,9 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         }
         wsync();
         evaluated = pr.ndm != 0;
-        const double lnl = evaluate(pr, evaluated, lp_new);
+        double lnl;
+        if constexpr (PROG) { if (counts) density_counts(); lnl = evaluate(pr, evaluated, lp_new, BoolC<true>{}); }
+        else lnl = evaluate(pr, evaluated, lp_new, BoolC<false>{});
         if (evaluated) { lnl_new = lnl; a_nupd += (uint32_t)nops; a_nbr += (uint32_t)__popc(pr.brm); ++a_neval; }
         const double dpr = program ? 0.0 : lp_new - logpr_cur;
         const double h = mix ? dpr + hast : (dpr + hast) + hast2;
@@ -1780,14 +1833,19 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
           else if (tid < (uint32_t)npop) wg.tau[tid] *= mix_c;
         }
       }
-      if (accept) { if (act) { lnl_cur = lnl_new; logpr_cur = lp_new; commit_density(allpop); } }
+      if (accept)
+      {
+        if constexpr (PROG) { if (act) { lnl_cur = lnl_new; if (li < npop) t2h_cur = t2h_new; } }      // (the counts stand: mync = mync_new since the first step)
+        else if (act) { lnl_cur = lnl_new; logpr_cur = lp_new; commit_density(allpop); }
+      }
       else if (act) { T.cf = cf0; T.pf = pf0; S->time[li] = tsave; }
       if constexpr (!PROG) __syncthreads();
       load_pop();
       wsync();
-      if (PROG && (refresh || accept) && act)
+      if (PROG && refresh && act)
       {
-        // the densities with the thetas as they are now (THETA's decisions, a TAU's or MIX's re-draws), from the statistics of the trees as settled
+        // once an iteration, behind MIX — the next reader is the sweep, a hand-over's record or the launch's store: the densities
+        // with the thetas as they are now (THETA's decisions, the TAUs' and MIX's re-draws), from the statistics of the trees as settled
         if (li < npop) S->contrib[li] = msc_term((int)mync, t2h_cur, pl.theta, pl.l2t);
         wsync();
         double lp = 0;
@@ -1807,13 +1865,13 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
         const bool first = stepq == nsp;
         step_begin(stepq);
         if (first && act && on) { fx_add(2*kidx, (double)mync, false); fx_add(2*kidx + 1, t2h_cur, false); }
-        step_locus(first ? nth : 0);
+        step_locus(first ? nth : 0, first);
         __syncthreads();                                                // B1: the terms are in
         if constexpr (HO) if (first && wvprof && lw == 0u) wg.b1last += (long long)wg.b1abs - wv_t0;      // (the sweep of the last wave to finish it)
         __syncthreads();                                                // B3: the decision is out (and the species tree as it now is, and the next proposal)
         const bool ab = wg.abort_ != 0u;
         accept = wg.dec.acc_step != 0u;
-        if (!ab) step_apply(first);
+        if (!ab) step_apply(stepq == npop);
         __syncthreads();                                                // B4: the next proposal is out
         if (ab) { aborted = true; break; }
       }
@@ -1899,7 +1957,7 @@ __global__ void __launch_bounds__(Cfg<NT>::BS) iter_kernel(const Args A)
     for (int stepq = nsp; stepq <= npop && !aborted; ++stepq)
     {
       step_begin(stepq);
-      step_locus(0);
+      step_locus(0, false);
       if (mix) SMP2_TICK(5); else SMP2_TICK(4);
       if (!mix && SP.parent[q] < 0 && SP.tau_alpha > 0)
         lnprior = (SP.tau_alpha - 1 - (nsp - 1) + 1)*log(tq_new/tq_old) - SP.tau_beta*(tq_new - tq_old);
