@@ -8,6 +8,7 @@ from .api import (BpaError, Engine, Locus, Plan, PlanSequence, Sampler, SamplerO
                   locus_update_all_matrices, locus_update_all_partials,
                   compute_gamma_cats, compress_site_patterns, map_nt, map_aa,
                   DATA_DNA, DATA_AA, MODEL_JC69, MODEL_GTR, MODEL_LG, SCALE_BUFFER_NONE,
+                  MODEL_K80, MODEL_F81, MODEL_HKY, MODEL_T92, MODEL_TN93, MODEL_F84,
                   ATTRIB_ARCH_HIP)
 
 __all__ = ["BpaError", "Engine", "Locus", "Plan", "RcclExchange", "GNode", "GTree", "Op", "OP_DTYPE", "lib",

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(HERE, "libbpp_amd.so")
 
 DATA_DNA, DATA_AA = 0, 1
 MODEL_JC69, MODEL_GTR, MODEL_LG = 0, 7, 10
+MODEL_K80, MODEL_F81, MODEL_HKY, MODEL_T92, MODEL_TN93, MODEL_F84 = 1, 2, 3, 4, 5, 6      # the closed-form DNA models (BPA_DNA_MODEL_*)
 ATTRIB_ARCH_HIP = 1 << 6
 SCALE_BUFFER_NONE = -1
 PARAM_FREQS, PARAM_SUBST, PARAM_RATES = 1, 2, 4
@@ -163,6 +164,8 @@ def lib():
         "bpa_sampler_set_subst_model": (i, [vp, u, dp, dp, d]),
         "bpa_sampler_get_subst_model": (i, [vp, u, dp, dp, dp]),
         "bpa_sampler_set_subst_moves": (None, [vp, d, d, d, d, d]),
+        "bpa_sampler_subst_steps": (i, [vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+        "bpa_sampler_set_qrates_prior": (i, [vp, dp]),
         "bpa_sampler_set_locus_rates": (i, [vp, dp]),
         "bpa_sampler_get_locus_rates": (i, [vp, dp, dp]),
         "bpa_sampler_set_locusrate_moves": (i, [vp, d, d, d, d, d, d]),
@@ -219,6 +222,7 @@ EXPORTED = ["bpa_version", "bpa_last_error", "bpa_device_count", "bpa_engine_cre
             "bpa_sampler_enable_timing", "bpa_sampler_timing", "bpa_sampler_work", "bpa_sampler_kind", "bpa_sampler_streams", "bpa_sampler_set_p2p", "bpa_sampler_set_proposal_kernel",
             "bpa_sampler_set_program_moves", "bpa_sampler_gibbs_counters",
             "bpa_sampler_set_subst_model", "bpa_sampler_get_subst_model", "bpa_sampler_set_subst_moves",
+            "bpa_sampler_subst_steps", "bpa_sampler_set_qrates_prior",
             "bpa_sampler_set_locus_rates", "bpa_sampler_get_locus_rates", "bpa_sampler_set_locusrate_moves", "bpa_sampler_locusrate_counters",
             "bpa_sampler_set_heredity", "bpa_sampler_get_heredity", "bpa_sampler_set_heredity_move", "bpa_sampler_heredity_counters",
             "bpa_sampler_set_trace", "bpa_sampler_trace_width", "bpa_sampler_trace_read"]
@@ -811,6 +815,21 @@ class Sampler:
         category keeps its alpha); every locus's starting values first (set_subst_model); a composite forwards the widths to
         its generic parts"""
         lib().bpa_sampler_set_subst_moves(self.h, ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b)
+
+    def subst_steps(self):
+        """(frequency steps, exchangeability steps) an iteration of this set runs: the most any locus's model has (GTR 3 and 5,
+        HKY / T92 / F84 3 and 1, TN93 3 and 2, F81 3 and 0, K80 0 and 1), 0 while that move's width is 0"""
+        f, q = C.c_uint(), C.c_uint()
+        _chk(lib().bpa_sampler_subst_steps(self.h, C.byref(f), C.byref(q)))
+        return f.value, q.value
+
+    def set_qrates_prior(self, a):
+        """the Dirichlet(a) prior on the exchangeabilities, a[6], for every model (default all ones: flat; the program's
+        values are (2, 4, 2, 2, 4, 2)); before initialize, on a sampler that has the substitution-parameter moves"""
+        a = _f64(a)
+        if a.shape != (6,):
+            raise ValueError("set_qrates_prior: six values")
+        _chk(lib().bpa_sampler_set_qrates_prior(self.h, _dp(a)))
 
     def set_locus_rates(self, mui):
         """the loci's mutation rates mu_i (each > 0), before initialize: every branch length is (t_parent - t_child) mu_i;

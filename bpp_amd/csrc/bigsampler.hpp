@@ -109,6 +109,7 @@ struct BArgs
   // was ever positive, no step of modes 6 - 8 is launched or settled
   double * sm, * sm_old;                  // [T][11] freqs | exchangeabilities | alpha of every locus; [T][2] the pending step's old values
   double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
+  double qprior[6]; uint32_t qprior_on, pad_qp;     // the Dirichlet prior on the exchangeabilities (bpa_sampler_set_qrates_prior); off: all ones
   uint8_t * par_todo;                     // [T] the components big_par_kernel owes the locus's parameter block: bit (mode - 6)
   const LocusDev * loci; const uint32_t * ids;      // the engine's loci and the sampler's ids among them (mode 8 reads the category count)
   uint32_t pend_k, pad_k;                 // pend == 4, modes 6 / 7: which component that step proposed
@@ -474,8 +475,11 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
     // sampler's copy — big_par_kernel brings the locus's parameter block level before the P-matrices are taken — then every
     // branch, every inner node; no age moves and the density stays.  A locus with one rate category has no alpha to move: it
     // proposes nothing and draws nothing (a00_driver.c:1187)
+    // A locus whose model has no step A.k of this kind (a00_subst_entry) sits it out the same way
     double * m = A.sm + (size_t)i*11;
-    if (!(MODE == 8 && A.loci[A.ids[i]].rate_cats < 2))
+    const LocusDev & LD = A.loci[A.ids[i]];
+    const int sj = MODE == 8 ? 0 : a00_subst_entry(MODE == 6 ? 1 : 2, (int)LD.model, (int)A.k);
+    if (!(MODE == 8 && LD.rate_cats < 2) && sj >= 0)
     {
       double hast;
       if (MODE == 8)
@@ -490,13 +494,14 @@ __device__ void big_propose(const BArgs & A, const uint32_t i, BTree & t, const 
       else
       {
         double * v = MODE == 6 ? m : m + 4;
-        const int j = (int)A.k, ref = MODE == 6 ? 3 : 1;                  // T / the A<->G rate (locus.c:2791, 3222)
+        const int j = sj, ref = a00_subst_ref(MODE == 6 ? 1 : 2, (int)LD.model);       // T / the model's reference rate (locus.c:2791, 3197-3229)
         const double sum = v[j] + v[ref], lo = log(1e-5), hi = log(sum);
-        const double l_old = log(v[j]);
+        const double l_old = log(v[j]), ref_old = v[ref];
         const double l_new = reflect(l_old + (MODE == 6 ? A.ft_freqs : A.ft_qrates)*rng.window(), lo, hi);
-        A.sm_old[2*i] = v[j]; A.sm_old[2*i + 1] = v[ref];
+        A.sm_old[2*i] = v[j]; A.sm_old[2*i + 1] = ref_old;
         v[j] = exp(l_new); v[ref] = sum - v[j];
         hast = l_new - l_old;                                               // locus.c:2867, 3296
+        if (MODE == 7 && A.qprior_on) hast += a00_qrates_prior_lnratio(A.qprior, j, ref, l_old, l_new, ref_old, v[ref]);
       }
       W.par_todo |= 1u << (MODE - 6);
       A.hast[i] = hast;
@@ -649,7 +654,13 @@ __global__ void __launch_bounds__(BBS) big_step_kernel(const BArgs A)
             back = true;
             double * m = A.sm + (size_t)i*11;
             if (A.pend_mode == 8) m[10] = A.sm_old[2*i];
-            else { double * v = A.pend_mode == 6 ? m : m + 4; const int ref = A.pend_mode == 6 ? 3 : 1; v[A.pend_k] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+            else
+            {
+              double * v = A.pend_mode == 6 ? m : m + 4;
+              const int wh = A.pend_mode == 6 ? 1 : 2, md = (int)A.loci[A.ids[i]].model, ref = a00_subst_ref(wh, md);
+              const int e = a00_subst_entry(wh, md, (int)A.pend_k);               // (>= 0: the locus was active in that step)
+              if (e >= 0) { v[e] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+            }
             s_w.par_todo |= 1u << (A.pend_mode - 6);
           }
         }
@@ -734,8 +745,8 @@ __global__ void __launch_bounds__(BBS) big_par_kernel(uint8_t * __restrict__ tod
   const uint32_t R = L.rate_cats;
   double * par = L.par;
   const double * m = sm + (size_t)i*11;
-  if (f & 1u) gsm::write_par(par, R, 6, m);
-  if (f & 2u) gsm::write_par(par, R, 7, m);
+  if (f & 1u) gsm::write_par(par, R, 6, m, L.model);
+  if (f & 2u) gsm::write_par(par, R, 7, m, L.model);
   if (f & 4u)
     switch (R)
     {
@@ -748,7 +759,7 @@ __global__ void __launch_bounds__(BBS) big_par_kernel(uint8_t * __restrict__ tod
       case 8: par_category_rates<8>(par, m[10]); break;
       default: break;                          // (one category: the step kernel proposes no alpha)
     }
-  if (f & 3u)
+  if ((f & 3u) && L.model == 100u)                // (a closed-form locus has no eigensystem: its P-matrices read the entries themselves)
   {
     double * pm = par + par_matrix(R, 4, 0);
     update_eigen_regs<4>(pm + pm_freqs(4), pm + pm_subst(4), pm + pm_evals(4), pm + pm_evecs(4), pm + pm_ievecs(4));

@@ -96,6 +96,8 @@ static int gb_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   if (mode == 10 && !a.hered) return fail("bpa_sampler: a heredity step without the scalars' array");
   a.sm = s->g_sm.p; a.sm_old = s->g_sm_old.p; a.pend_k = s->g_pend_k; a.par_todo = s->b_par_todo.p; a.loci = e->d_loci.p; a.ids = s->g_ids.p;
   a.ft_freqs = s->g_ft[0]; a.ft_qrates = s->g_ft[1]; a.ft_alpha = s->g_ft[2]; a.alpha_a = s->g_alpha_a; a.alpha_b = s->g_alpha_b;
+  for (int q = 0; q < 6; ++q) a.qprior[q] = s->g_qprior[q];
+  a.qprior_on = s->g_qprior_on ? 1u : 0u;
   const bool par_step = mode >= 6 && mode <= 8, par_settled = s->g_pend == 4 && s->g_pend_mode >= 6 && s->g_pend_mode <= 8;
   if ((par_step || par_settled) && !(a.sm && a.par_todo)) return fail("bpa_sampler: a substitution-parameter step without the moves' tables");
   a.sp = s->sp;
@@ -212,8 +214,10 @@ static int gb_mubar(bpa_sampler * s)
 static int gb_scalars(bpa_sampler * s)
 {
   if (s->g_h_ft > 0) { if (!gb_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
-  if (s->g_ft[0] > 0) for (unsigned j = 0; j < 3; ++j)  { if (!gb_step(s, 6, j) || !gb_eval(s, 0)) return 0; }
-  if (s->g_ft[1] > 0) for (unsigned j = 0; j < 6; ++j)  { if (j != 1 && (!gb_step(s, 7, j) || !gb_eval(s, 0))) return 0; }
+  unsigned nfreq = 0, nqr = 0;
+  subst_step_counts(s, &nfreq, &nqr);
+  for (unsigned j = 0; j < nfreq; ++j) { if (!gb_step(s, 6, j) || !gb_eval(s, 0)) return 0; }
+  for (unsigned j = 0; j < nqr; ++j)   { if (!gb_step(s, 7, j) || !gb_eval(s, 0)) return 0; }
   if (s->g_ft[2] > 0)                                   { if (!gb_step(s, 8, 0) || !gb_eval(s, 0)) return 0; }
   if (gb_subst_moves(s))
     for (bpa_locus * l : s->loci) l->host_par_stale = true;              // the device blocks moved ahead of the host mirrors

@@ -45,7 +45,7 @@ static_assert(sizeof(GTree) % 16 == 0, "GTree is copied as uint4");
 struct GLocus                             // what never changes, per locus
 {
   uint32_t slot, pat_off;                 // its slot of the engine's packing, first pattern in the step's term array
-  uint32_t R, pad;                        // rate categories
+  uint32_t R, model;                      // rate categories; LocusDev::model (0 JC69, 1..6 the closed forms, 100 eigendecomposition): which entries its parameter moves have
   double * par;                           // the locus's parameter block (device_types.hpp): the substitution-parameter moves write it
   alignas(16) int8_t gl[MAXPOP];          // gene tips below each population
   alignas(16) int8_t nin[MAXPOP];         // gene tips of each species
@@ -77,7 +77,7 @@ struct GArgs
   uint32_t k;
   uint32_t pend;                          // the step to settle first: 0 none, 1 per-locus decisions, 2 an all-loci decision (flag / epoch),
                                           // 3 commit (start-up), 4 per-locus decisions of a substitution-parameter step
-  uint32_t pend_mode, pend_k;             // pend 4: which component that step proposed
+  uint32_t pend_mode, pend_k;             // pend 4: which component that step proposed (modes 6 / 7: the step's ordinal, a00_subst_entry)
   // per-locus mutation rates (bpa_sampler_set_locus_rates): every branch length a step writes or uses is (t_parent - t_child) mu_i
   // (locus.c:2350).  mui == null: no rates were ever set, every mu_i is 1 and no load is made
   double * mui, * mui_old;                // [T] the rates; [T] a pending mode-9 step's old values
@@ -90,6 +90,7 @@ struct GArgs
   double ft_h, h_a, h_b;                  // mode 10 (HRDT): window width, the gamma(a, b) prior
   double * sm, * sm_old;                  // [T][11] freqs | exchangeabilities | alpha of every locus; [T][2] the pending step's old values
   double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
+  double qprior[6]; uint32_t qprior_on, pad_qp;     // the Dirichlet prior on the exchangeabilities (bpa_sampler_set_qrates_prior); off: all ones
   const double * lnl_new;                 // [T] lnL of the pending step's evaluation (task = locus)
   double * hast, * logpr_new;             // [T] Hastings term / proposed MSC density of the step being proposed (read back when it is settled)
   double * delta;                         // [T] an all-loci step: this locus's density + Jacobian term
@@ -194,10 +195,11 @@ __global__ void glograt_kernel(double * tab)         // log(i/j), i, j < NN
 }
 
 // component `mode` (6 frequencies, 7 exchangeabilities, 8 alpha -> category rates) of a locus's values into its parameter block
-__device__ __forceinline__ void write_par(double * par, uint32_t R, uint32_t mode, const double * m)
+// (the exchangeabilities: the entries the locus's model has, a00_subst_qrates)
+__device__ __forceinline__ void write_par(double * par, uint32_t R, uint32_t mode, const double * m, const uint32_t model)
 {
   if (mode == 6)      for (int q = 0; q < 4; ++q) par[par_matrix(R, 4, 0) + pm_freqs(4) + q] = m[q];
-  else if (mode == 7) for (int q = 0; q < 6; ++q) par[par_matrix(R, 4, 0) + pm_subst(4) + q] = m[4 + q];
+  else if (mode == 7) { const int nq = a00_subst_qrates((int)model); for (int q = 0; q < nq; ++q) par[par_matrix(R, 4, 0) + pm_subst(4) + q] = m[4 + q]; }
   else
   {
     double rates[8];
@@ -309,7 +311,13 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
           back = true;
           double * m = A.sm + (size_t)i*11;
           if (A.pend_mode == 8) m[10] = A.sm_old[2*i];
-          else { double * v = A.pend_mode == 6 ? m : m + 4; const int ref = A.pend_mode == 6 ? 3 : 1; v[A.pend_k] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+          else
+          {
+            double * v = A.pend_mode == 6 ? m : m + 4;
+            const int wh = A.pend_mode == 6 ? 1 : 2, ref = a00_subst_ref(wh, (int)L.model);
+            const int e = a00_subst_entry(wh, (int)L.model, (int)A.pend_k);       // (>= 0: the locus was active in that step)
+            if (e >= 0) { v[e] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+          }
           restore_par = true;
         }
         }
@@ -389,7 +397,9 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
     {
       // a substitution-parameter move (param_step of a00_driver.c): new value, then every branch, every inner node
       double * m = MODE == 9 ? nullptr : A.sm + (size_t)i*11;
-      if (MODE == 8 && L.R < 2) ok = false;
+      // (a locus whose model has no step A.k of this kind sits it out: nothing proposed, nothing drawn, nothing counted)
+      const int sj = (MODE == 6 || MODE == 7) ? a00_subst_entry(MODE == 6 ? 1 : 2, (int)L.model, (int)A.k) : 0;
+      if ((MODE == 8 && L.R < 2) || sj < 0) ok = false;
       else
       {
         if (MODE == 9)
@@ -414,13 +424,14 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
         else
         {
           double * v = MODE == 6 ? m : m + 4;
-          const int j = (int)A.k, ref = MODE == 6 ? 3 : 1;
+          const int j = sj, ref = a00_subst_ref(MODE == 6 ? 1 : 2, (int)L.model);
           const double sum = v[j] + v[ref], lo = log(1e-5), hi = log(sum);
-          const double l_old = log(v[j]);
+          const double l_old = log(v[j]), ref_old = v[ref];
           const double l_new = reflect(l_old + (MODE == 6 ? A.ft_freqs : A.ft_qrates)*g_window(T.rng, A.bpp), lo, hi);
-          A.sm_old[2*i] = v[j]; A.sm_old[2*i + 1] = v[ref];
+          A.sm_old[2*i] = v[j]; A.sm_old[2*i + 1] = ref_old;
           v[j] = exp(l_new); v[ref] = sum - v[j];
           hast = l_new - l_old;
+          if (MODE == 7 && A.qprior_on) hast += a00_qrates_prior_lnratio(A.qprior, j, ref, l_old, l_new, ref_old, v[ref]);
         }
         propose_par = MODE != 9;
         const int nn_ = 2*T.tips - 1;
@@ -478,14 +489,14 @@ __global__ void __launch_bounds__(GBS) gstep_kernel(const GArgs A)
       if (!on) continue;
       // (restored and proposed component may be the same one: this order leaves the proposal in the block.  NB the
       //  values of `m` are final here — a restored component and a newly proposed one never overlap in time)
-      write_par(L.par, L.R, md, m);
+      write_par(L.par, L.R, md, m, L.model);
     }
     // (round 6) K6 right here: the lane that moved its locus's frequencies / exchangeabilities (proposed new ones, or put a rejected
     // proposal's back) refreshes the eigensystem of the block's rate matrix 0 — the one these moves write — in the same launch.
     // It was a launch of its own (eigen_kernel over ALL loci: 20 us + a launch boundary) between every parameter proposal and its
     // P-matrices: 16 launches of an iteration of config 3.  Same routine, same inputs, same bits.
     const bool eig = (restore_par && (A.pend_mode == 6 || A.pend_mode == 7)) || (propose_par && (MODE == 6 || MODE == 7));
-    if (A.fuse_eigen && eig)
+    if (A.fuse_eigen && eig && L.model == 100u)                     // (a closed-form locus has no eigensystem to keep level)
     {
       double * pm = L.par + par_matrix(L.R, 4, 0);
       update_eigen_regs<4>(pm + pm_freqs(4), pm + pm_subst(4), pm + pm_evals(4), pm + pm_evecs(4), pm + pm_ievecs(4));

@@ -190,7 +190,13 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
           {
             double * m = A.sm + (size_t)i*11;
             if (A.pend_mode == 8) m[10] = A.sm_old[2*i];
-            else { double * v = A.pend_mode == 6 ? m : m + 4; const int ref = A.pend_mode == 6 ? 3 : 1; v[A.pend_k] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+            else
+            {
+              double * v = A.pend_mode == 6 ? m : m + 4;
+              const int wh = A.pend_mode == 6 ? 1 : 2, ref = a00_subst_ref(wh, (int)L.model);
+              const int e = a00_subst_entry(wh, (int)L.model, (int)A.pend_k);     // (>= 0: the locus was active in that step)
+              if (e >= 0) { v[e] = A.sm_old[2*i]; v[ref] = A.sm_old[2*i + 1]; }
+            }
           }
           restore_par = true;
         }
@@ -219,7 +225,7 @@ __device__ __forceinline__ void gstep2_body(const gsm::GArgs & A, const StepCtl 
     S.time[li] = valid && li < n0 ? (back ? u_time : g_time) : 0.0;
   }
   smp2::wsync();
-  if (valid && restore_par && li == 0) gsm::write_par(L.par, L.R, A.pend_mode, A.sm + (size_t)i*11);
+  if (valid && restore_par && li == 0) gsm::write_par(L.par, L.R, A.pend_mode, A.sm + (size_t)i*11, L.model);
 
   GS2_T(3);
   const int tips = T.tips, n = 2*tips - 1;

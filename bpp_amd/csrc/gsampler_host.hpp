@@ -22,6 +22,20 @@ static int gs_subst_ready(bpa_sampler * s)
   return 1;
 }
 
+// how many frequency / exchangeability steps an iteration runs: the most any locus's model has (a00_subst_steps of
+// bpp_amd_priors.h; LocusDev::model 100 moves as GTR), none while that move's width is 0
+static void subst_step_counts(const bpa_sampler * s, unsigned * nfreq, unsigned * nqr)
+{
+  int f = 0, q = 0;
+  for (const bpa_locus * l : s->loci)
+  {
+    f = std::max(f, a00_subst_steps(1, (int)l->dev.model));
+    q = std::max(q, a00_subst_steps(2, (int)l->dev.model));
+  }
+  *nfreq = s->g_ft[0] > 0 ? (unsigned)f : 0u;
+  *nqr = s->g_ft[1] > 0 ? (unsigned)q : 0u;
+}
+
 // the per-locus rates' device arrays (rates, a pending step's old values, their mean): made when rates were set or a
 // locus-rate move is on — a sampler that never heard of rates passes null pointers, which its kernels read as "every rate 1"
 static bool gs_lr_moves(const bpa_sampler * s) { return s->g_lr_ft[0] > 0 || s->g_lr_ft[1] > 0; }
@@ -57,6 +71,7 @@ static int gs_refresh_eigen(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
   if (!s->g_eigen_dirty) return 1;
+  if (!s->g_any_eigen) { s->g_eigen_dirty = false; return 1; }        // (closed-form loci only: nothing to refresh, no launch)
   if (!s->g_ids.p)
   {
     std::vector<uint32_t> ids(s->nloci);
@@ -125,7 +140,7 @@ static int gs_upload(bpa_sampler * s)
     for (int k = 0; k < t.tips; ++k) if (++cnt[t.pop[k]] >= 2) s->has_theta[t.pop[k]] = true;
     if (!s->g_s20 && e->slot_of[l->id] < 0) return fail("bpa_sampler: a locus is not on the engine's packing");
     gsm::GLocus & g = loc[i];
-    g.slot = s->g_s20 ? i : (uint32_t)e->slot_of[l->id]; g.pat_off = npat; g.R = l->rate_cats; g.pad = 0; g.par = l->dev.par;
+    g.slot = s->g_s20 ? i : (uint32_t)e->slot_of[l->id]; g.pat_off = npat; g.R = l->rate_cats; g.model = l->dev.model; g.par = l->dev.par;
     for (int p = 0; p < smp::MAXPOP; ++p) g.gl[p] = g.nin[p] = 0;
     for (int k = 0; k < t.tips; ++k)
     {
@@ -134,6 +149,8 @@ static int gs_upload(bpa_sampler * s)
     }
     npat += l->sites;
   }
+  s->g_any_eigen = false;
+  for (const bpa_locus * l : s->loci) s->g_any_eigen = s->g_any_eigen || l->dev.model == 100u;
   s->g_npat = npat;
   s->g_units = 1 + std::max(s->maxtips - 1, 3u);
   s->g_maxmat = 2*s->maxtips - 2;
@@ -322,6 +339,8 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   a.fmt20 = s->g_s20 ? 1u : 0u; a.maxops20 = s->g_maxops;
   a.ops20 = s->g_ops20.p; a.op_rng20 = s->g_oprng.p; a.root20 = s->g_root20.p; a.mat_task20 = s->g_mtask.p; a.mat_pm20 = s->g_mpm.p;
   a.ft_freqs = s->g_ft[0]; a.ft_qrates = s->g_ft[1]; a.ft_alpha = s->g_ft[2]; a.alpha_a = s->g_alpha_a; a.alpha_b = s->g_alpha_b;
+  for (int q = 0; q < 6; ++q) a.qprior[q] = s->g_qprior[q];
+  a.qprior_on = s->g_qprior_on ? 1u : 0u;
   a.bpp = s->kernel_bpp ? 1u : 0u; a.prog = gs_prog(s) ? 1u : 0u; a.t2h3 = s->g_t2h3.p; a.tau_w = tau_w;
   a.slot_tab = e->d_slot_tab.p;
   gs_lr_args(s, a);
@@ -333,7 +352,8 @@ static int gs_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u 
   // parameter blocks whose eigensystems are stale: refreshed before the next evaluation (gs_eval)
   // ... unless the launch is the one-lane kernel (settle, start-up, the parameter moves) on 4-state loci whose eigensystems are
   // level now: its lanes then refresh what they write themselves (GArgs::fuse_eigen, round 6) and nothing is left stale
-  const bool touches_eigen = mode == 6 || mode == 7 || (s->g_pend == 4 && (s->g_pend_mode == 6 || s->g_pend_mode == 7));
+  // (only loci with an eigendecomposition are owed anything: a set of closed-form loci never touches one)
+  const bool touches_eigen = s->g_any_eigen && (mode == 6 || mode == 7 || (s->g_pend == 4 && (s->g_pend_mode == 6 || s->g_pend_mode == 7)));
   a.fuse_eigen = (touches_eigen && mode >= 4 && mode != 10 && !s->g_s20 && !s->g_alljc && e->usedata && !s->g_eigen_dirty) ? 1u : 0u;
   if (touches_eigen && !a.fuse_eigen) s->g_eigen_dirty = true;
   // diagnostics (the options' diff): a GAGE / GSPR step by both kernels from the same state, whatever differs is reported;
@@ -1259,8 +1279,11 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
     // launch per part-batch that settles MIX, proposes and decides — no evaluation, nothing pending afterwards
     if (s->g_h_ft > 0) { if (!gs_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
     // the substitution-parameter moves come last (method.c:5699-5735; param_step of a00_driver.c)
-    if (s->g_ft[0] > 0) for (unsigned j = 0; j < 3; ++j)  { if (!gs_step(s, 6, j) || !gs_eval(s, 0)) return 0; }
-    if (s->g_ft[1] > 0) for (unsigned j = 0; j < 6; ++j)  { if (j != 1 && (!gs_step(s, 7, j) || !gs_eval(s, 0))) return 0; }
+    // (as many steps of a kind as the loci's models have at most, a00_subst_steps: GTR 3 + 5, HKY 3 + 1, K80 0 + 1)
+    unsigned nfreq = 0, nqr = 0;
+    subst_step_counts(s, &nfreq, &nqr);
+    for (unsigned j = 0; j < nfreq; ++j) { if (!gs_step(s, 6, j) || !gs_eval(s, 0)) return 0; }
+    for (unsigned j = 0; j < nqr; ++j)   { if (!gs_step(s, 7, j) || !gs_eval(s, 0)) return 0; }
     if (s->g_ft[2] > 0)                                   { if (!gs_step(s, 8, 0) || !gs_eval(s, 0)) return 0; }
     if (s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0)
       for (bpa_locus * l : s->loci) l->host_par_stale = true;            // the device blocks moved ahead of the host mirrors
@@ -1312,6 +1335,35 @@ static int gs_download(bpa_sampler * s)
 }
 
 // ---- substitution-parameter moves: the sampler's copy of every locus's values and the window widths
+extern "C" int bpa_sampler_subst_steps(bpa_sampler_t * s, unsigned * freq_steps, unsigned * qrate_steps)
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  unsigned nf = 0, nq = 0;
+  if (s->comp) (void)comp_each(s, [&](bpa_sampler * p) { unsigned f = 0, q = 0; if (p->generic) subst_step_counts(p, &f, &q); nf = std::max(nf, f); nq = std::max(nq, q); return 1; });
+  else if (s->generic || s->big) subst_step_counts(s, &nf, &nq);
+  if (freq_steps) *freq_steps = nf;
+  if (qrate_steps) *qrate_steps = nq;
+  return 1;
+}
+
+extern "C" int bpa_sampler_set_qrates_prior(bpa_sampler_t * s, const double a[6])
+{
+  std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);
+  if (!a) return fail("bpa_sampler_set_qrates_prior: null argument");
+  for (int q = 0; q < 6; ++q) if (!(a[q] > 0) || !std::isfinite(a[q])) return fail("bpa_sampler_set_qrates_prior: every parameter is > 0 and finite");
+  if (s->comp) return comp_each(s, [&](bpa_sampler * p) { return p->generic ? bpa_sampler_set_qrates_prior(p, a) : 1; });
+  if (!s->generic && !s->big) return fail("bpa_sampler_set_qrates_prior: the loci are JC69 (no substitution parameters to move)");
+  {
+    bool anypar = false;
+    for (const bpa_locus * l : s->loci) anypar = anypar || (l->states == 4 && l->dev.model != 0u);
+    if (!anypar) return fail("bpa_sampler_set_qrates_prior: the loci are JC69 (no substitution parameters to move)");
+  }
+  if (s->uploaded)
+    return fail("bpa_sampler_set_qrates_prior: the sampler is running — set the prior before bpa_sampler_initialize");
+  std::copy(a, a + 6, s->g_qprior);
+  s->g_qprior_on = !a00_qrates_prior_flat(a);
+  return 1;
+}
 extern "C" int bpa_sampler_set_subst_model(bpa_sampler_t * s, unsigned i, const double * freqs, const double * qrates, double alpha)
 {
   std::lock_guard<std::recursive_mutex> lock_(s->eng->mtx);

@@ -60,6 +60,8 @@ struct a00_driver
   double * sm; int * sm_ncat; a00_param_fn setpar;
   double ft_freqs, ft_qrates, ft_alpha, alpha_a, alpha_b;
   double * sm_old;                      /* proposed component's old values per slot: [2] for freqs / qrates, alpha */
+  int * sm_kind;                        /* [nloci] the model whose entries locus i moves (a00_set_subst_kind); NULL: every locus GTR */
+  double qprior[6]; int qprior_on;      /* the Dirichlet prior on the exchangeabilities (a00_set_qrates_prior); off: all ones */
   /* per-locus mutation rates (a00_set_locus_rates / a00_set_locusrate_moves): the rates themselves are the trees' rate_mui */
   double * mui, * mui_old;              /* what a00_set_locus_rates left (a tree set afterwards starts from it); a pending MUI step's old values */
   double ft_mui, ft_mubar, a_mui, a_mubar, b_mubar, mubar;
@@ -172,6 +174,7 @@ a00_driver_t * a00_create(unsigned nloci, a00_eval_fn eval, void * ctx, unsigned
   a00_driver_t * d = (a00_driver_t *)calloc(1, sizeof(*d));
   unsigned q;
   d->nloci = nloci; d->eval = eval; d->ctx = ctx;
+  for (q = 0; q < 6; ++q) d->qprior[q] = 1.0;
   d->rng = (a00_rng_t *)calloc(nloci, sizeof(a00_rng_t));
   for (q = 0; q < nloci; ++q) d->rng[q] = a00_rng_seed(seed, q);
   d->grng = a00_rng_seed(seed, A00_GLOBAL_STREAM);
@@ -221,7 +224,7 @@ void a00_destroy(a00_driver_t * d)
   }
   d->view[d->cur_view].s_br = d->s_br; d->view[d->cur_view].s_nd = d->s_nd;
   { int v; for (v = 0; v < 3; ++v) { free(d->view[v].s_br); free(d->view[v].s_nd); } }
-  free(d->rng); free(d->zrng); free(d->sm); free(d->sm_ncat); free(d->sm_old); free(d->mui); free(d->mui_old); free(d->hered); free(d->trees); free(d->b_locus); free(d->b_tree); free(d->b_br_off); free(d->b_nd_off);
+  free(d->rng); free(d->zrng); free(d->sm); free(d->sm_ncat); free(d->sm_old); free(d->sm_kind); free(d->mui); free(d->mui_old); free(d->hered); free(d->trees); free(d->b_locus); free(d->b_tree); free(d->b_br_off); free(d->b_nd_off);
   free(d->t_br_off); free(d->t_nd_off);
   free(d->b_logpr); free(d->p_logpr); free(d->p_delta); free(d->p_slot); free(d->u_pop);
   free(d->w_br); free(d->w_nd); free(d->w_nb); free(d->w_nn); free(d->w_hast); free(d->w_logpr); free(d->w_diff);
@@ -1180,6 +1183,49 @@ int a00_get_subst_model(const a00_driver_t * d, unsigned i, double * freqs, doub
   if (alpha) *alpha = m[10];
   return 1;
 }
+int a00_set_subst_kind(a00_driver_t * d, unsigned i, int model)
+{
+  unsigned q;
+  if (i >= d->nloci || model < 1 || model > 7) return 0;            /* (JC69 has nothing to move) */
+  if (!d->sm_kind)
+  {
+    d->sm_kind = (int *)malloc(d->nloci*sizeof(int));
+    if (!d->sm_kind) return 0;
+    for (q = 0; q < d->nloci; ++q) d->sm_kind[q] = 7;
+  }
+  d->sm_kind[i] = model;
+  return 1;
+}
+int a00_set_qrates_prior(a00_driver_t * d, const double a[6])
+{
+  int q;
+  if (!a) return 0;
+  for (q = 0; q < 6; ++q) if (!(a[q] > 0) || !(a[q] < INFINITY)) return 0;
+  for (q = 0; q < 6; ++q) d->qprior[q] = a[q];
+  d->qprior_on = !a00_qrates_prior_flat(a);
+  return 1;
+}
+/* the compiled expressions of bpp_amd_priors.h, for a caller without a C compiler (the tests) */
+double a00_qrates_prior_piece(const double a[6], int j, int ref, double qj_old, double qj_new, double qref_old, double qref_new)
+{
+  return a00_qrates_prior_lnratio(a, j, ref, log(qj_old), log(qj_new), qref_old, qref_new);
+}
+int a00_subst_table(int model, int which, int step, int * entry, int * ref, int * steps)
+{
+  if (entry) *entry = a00_subst_entry(which, model, step);
+  if (ref) *ref = a00_subst_ref(which, model);
+  if (steps) *steps = a00_subst_steps(which, model);
+  return a00_subst_qrates(model);
+}
+static int subst_kind(const a00_driver_t * d, unsigned i) { return d->sm_kind ? d->sm_kind[i] : 7; }
+/* how many steps of a kind (1 frequencies, 2 exchangeabilities) an iteration runs: the loci's maximum */
+static int subst_steps_max(const a00_driver_t * d, int which)
+{
+  unsigned i; int n = 0;
+  for (i = 0; i < d->nloci; ++i) { const int k = a00_subst_steps(which, subst_kind(d, i)); if (k > n) n = k; }
+  return n;
+}
+
 /* hand the current values of component `which` of locus i to the likelihood back-end */
 static int push_param(a00_driver_t * d, unsigned i, int which)
 {
@@ -1196,11 +1242,11 @@ static int push_param(a00_driver_t * d, unsigned i, int which)
   }
 }
 
-/* one component (which = 1 frequency j, 2 exchangeability j, 4 alpha) of every locus: propose, full recomputation, decide */
-static int param_step(a00_driver_t * d, int which, int j)
+/* one component (which = 1 frequencies, 2 exchangeabilities: the step'th moving entry of each locus's model; 4 alpha) of
+   every locus: propose, full recomputation, decide.  A locus whose model has no such step sits it out */
+static int param_step(a00_driver_t * d, int which, int step)
 {
   unsigned i, n = 0, s;
-  const int ref = which == 1 ? 3 : 1;                      /* T / the A<->G rate (locus.c:2791, 3222) */
   if (!staging_ready(d)) return 0;
   for (i = 0; i < d->nloci; ++i) d->w_nb[i] = -1;
   for (i = 0; i < d->nloci; ++i)
@@ -1208,7 +1254,10 @@ static int param_step(a00_driver_t * d, int which, int j)
     a00_tree_t * t = d->trees + i; double * m = d->sm + (size_t)i*11;
     int br[MAXN], nd[MAXN], nb = 0, nn = 0, k;
     double hast;
+    const int j = which == 4 ? 0 : a00_subst_entry(which, subst_kind(d, i), step);
+    const int ref = a00_subst_ref(which, subst_kind(d, i));  /* T / the model's reference rate (locus.c:2791, 3197-3229) */
     if (which == 4 && d->sm_ncat[i] < 2) continue;
+    if (j < 0) continue;
     if (which == 4)
     {
       const double a_old = m[10], la_old = log(a_old);
@@ -1227,6 +1276,7 @@ static int param_step(a00_driver_t * d, int which, int j)
       d->sm_old[2*n] = v[j]; d->sm_old[2*n+1] = v[ref];
       v[j] = exp(l_new); v[ref] = sum - v[j];
       hast = l_new - l_old;                                                                              /* locus.c:2867, 3296 */
+      if (which == 2 && d->qprior_on) hast += a00_qrates_prior_lnratio(d->qprior, j, ref, l_old, l_new, d->sm_old[2*n+1], v[ref]);
     }
     if (!push_param(d, i, which)) return 0;
     snapshot(d, i);
@@ -1247,7 +1297,12 @@ static int param_step(a00_driver_t * d, int which, int j)
     if (accept(d, (long)li, lnacc, -1.0)) { t->lnl = d->s_lnl[s]; d->accepted++; continue; }
     restore(d, li);
     if (which == 4) m[10] = d->sm_old[2*s];
-    else { double * v = which == 1 ? m : m + 4; v[j] = d->sm_old[2*s]; v[ref] = d->sm_old[2*s+1]; }
+    else
+    {
+      double * v = which == 1 ? m : m + 4;
+      const int j = a00_subst_entry(which, subst_kind(d, li), step), ref = a00_subst_ref(which, subst_kind(d, li));
+      v[j] = d->sm_old[2*s]; v[ref] = d->sm_old[2*s+1];
+    }
     if (!push_param(d, li, which)) return 0;
   }
   return 1;
@@ -1421,8 +1476,9 @@ int a00_iterate(a00_driver_t * d)
   /* the substitution-parameter moves come last (method.c:5699-5735) */
   if (d->sm && d->setpar)
   {
-    if (d->ft_freqs > 0)  for (k = 0; k < 3; ++k) if (!param_step(d, 1, k)) return 0;
-    if (d->ft_qrates > 0) for (k = 0; k < 6; ++k) if (k != 1 && !param_step(d, 2, k)) return 0;
+    const int nfreq = subst_steps_max(d, 1), nqr = subst_steps_max(d, 2);
+    if (d->ft_freqs > 0)  for (k = 0; k < nfreq; ++k) if (!param_step(d, 1, k)) return 0;
+    if (d->ft_qrates > 0) for (k = 0; k < nqr; ++k)   if (!param_step(d, 2, k)) return 0;
     if (d->ft_alpha > 0 && !param_step(d, 4, 0)) return 0;
   }
   /* ... then the loci's rates and their mean (method.c:5745-5773); a fixed mean (a_mubar = b_mubar = 0) draws nothing */

@@ -2479,9 +2479,10 @@ step_s4_klane_v2_kernel(const PlanDev P)
     if (lane < q1 - q0)
     {
       const LocusDev & L = P.loci[P.slot_tab[q0 + lane].locus];
-      // (a JC69 locus — the other loci of a composite's packing — has no eigensystem.  NOT "only the loci with a record in this
-      //  step": a locus whose rejected parameter proposal was just rolled back may sit this step out, and the refresh is owed once)
-      const bool mine = L.model != 0u;
+      // (a JC69 locus — the other loci of a composite's packing — has no eigensystem, and neither has a closed-form one.  NOT "only
+      //  the loci with a record in this step": a locus whose rejected parameter proposal was just rolled back may sit this step
+      //  out, and the refresh is owed once)
+      const bool mine = L.model == 100u;
       for (uint32_t m = 0; mine && m < L.rate_matrices; ++m)
       {
         double * pm = L.par + par_matrix(L.rate_cats, 4, m);
@@ -2745,9 +2746,10 @@ step_s4_klane_v3_kernel(const PlanDev P)
     if (lane < q1 - q0)
     {
       const LocusDev & L = P.loci[P.slot_tab[q0 + lane].locus];
-      // (a JC69 locus — the other loci of a composite's packing — has no eigensystem.  NOT "only the loci with a record in this
-      //  step": a locus whose rejected parameter proposal was just rolled back may sit this step out, and the refresh is owed once)
-      const bool mine = L.model != 0u;
+      // (a JC69 locus — the other loci of a composite's packing — has no eigensystem, and neither has a closed-form one.  NOT "only
+      //  the loci with a record in this step": a locus whose rejected parameter proposal was just rolled back may sit this step
+      //  out, and the refresh is owed once)
+      const bool mine = L.model == 100u;
       for (uint32_t m = 0; mine && m < L.rate_matrices; ++m)
       {
         double * pm = L.par + par_matrix(L.rate_cats, 4, m);
@@ -3745,6 +3747,7 @@ __global__ void __launch_bounds__(64) eigen_kernel(const LocusDev * loci, const 
   const uint32_t i = blockIdx.x*64 + threadIdx.x;
   if (i >= count) return;
   const LocusDev & L = loci[list[i]];
+  if (L.model != 100u) return;                    // (JC69 and the closed-form models have no eigensystem; a sampler's list holds all its loci)
   const uint32_t R = L.rate_cats, S = SK ? (uint32_t)SK : L.states;
   for (uint32_t m = 0; m < L.rate_matrices; ++m)
   {

@@ -1210,6 +1210,8 @@ struct bpa_sampler
   DevBuf<double> g_sm, g_sm_old;
   DevBuf<uint32_t> g_ids;
   double g_ft[3] = {0, 0, 0}, g_alpha_a = 1, g_alpha_b = 1;
+  double g_qprior[6] = {1, 1, 1, 1, 1, 1}; bool g_qprior_on = false;      // bpa_sampler_set_qrates_prior
+  bool g_any_eigen = true;                // a locus with an eigendecomposition among the sampler's (set at the upload): only those are owed K6 after a parameter step
   unsigned g_pend_mode = 0, g_pend_k = 0;
   // per-locus mutation rates (bpa_sampler_set_locus_rates / bpa_sampler_set_locusrate_moves): the rates and a pending rate
   // step's old values in arrays of their own ([T] doubles; never made when no rate is set and no move is on), their mean and

@@ -175,19 +175,45 @@ def scaled_tree(t, f):
     return t if isinstance(t, str) else (scaled_tree(t[0], f), scaled_tree(t[1], f), t[2]*f)
 
 
+# the closed-form DNA models (K7, pmatrix_dna_closed): name -> (the model's own exchangeability entries for a transition /
+# transversion ratio kappa, padded to six with ones: what the locus holds; the six GTR exchangeabilities AC AG AT CG CT GT of the
+# same rate matrix: what the simulation runs).  K80 / HKY: kappa = q1/q0; T92 / F84: kappa = q0/q1, F84's transition rates are
+# 1 + kappa/R and 1 + kappa/Y; TN93: q0/q2 the pyrimidines' (C<->T) and q1/q2 the purines' (A<->G) ratio, here kappa and 0.8 kappa
+CLOSED_FORM = ("k80", "f81", "hky", "t92", "tn93", "f84")
+
+
+def closed_form_rates(model, kappa, freqs):
+    """(qrates[6] of the locus, exch[6] of the equivalent GTR matrix) of a closed-form model"""
+    A, Cc, G, T = freqs
+    one = [1.0]*6
+    if model == "f81":
+        return np.array(one), np.array(one)
+    if model in ("k80", "hky"):
+        return np.array([1.0, kappa, 1, 1, 1, 1]), np.array([1, kappa, 1, 1, kappa, 1.0])
+    if model == "t92":
+        return np.array([kappa, 1.0, 1, 1, 1, 1]), np.array([1, kappa, 1, 1, kappa, 1.0])
+    if model == "tn93":
+        return np.array([kappa, 0.8*kappa, 1.0, 1, 1, 1]), np.array([1, 0.8*kappa, 1, 1, kappa, 1.0])
+    if model == "f84":
+        return np.array([kappa, 1.0, 1, 1, 1, 1]), np.array([1, 1 + kappa/(A + G), 1, 1, 1 + kappa/(T + Cc), 1.0])
+    raise ValueError(model)
+
+
 def make_dataset(nloci, sites, taxa=4, model="jc69", rate_cats=1, alpha=0.5, theta=None, seed=12345,
-                 freqs=None, exch=None, divergence=1.0):
+                 freqs=None, exch=None, divergence=1.0, kappa=2.0):
     """returns a list of loci: dict(seqs (compressed), weights, left, right, times, root, ...).
     divergence: every tau of SPECIES_TREES[taxa] and the default theta times this factor (more substitutions per site:
-    more distinct site patterns per locus)"""
-    cached = _cache_file(nloci, sites, taxa, model, rate_cats, alpha, theta, seed, divergence) if freqs is None and exch is None else None
+    more distinct site patterns per locus).
+    model "k80" | "f81" | "hky" | "t92" | "tn93" | "f84": simulated as the GTR special case it is, transition / transversion
+    ratio kappa; the loci carry the model's own entries in "exch" (closed_form_rates)"""
+    cached = _cache_file(nloci, sites, taxa, model, rate_cats, alpha, theta, seed, divergence) if freqs is None and exch is None and kappa == 2.0 else None
     if cached and os.path.exists(cached):
         import pickle
         with open(cached, "rb") as f:
             return pickle.load(f)
     rng = np.random.default_rng(seed)
     stree = scaled_tree(SPECIES_TREES[taxa], divergence)
-    dna = model in ("jc69", "gtr")
+    dna = model in ("jc69", "gtr") or model in CLOSED_FORM
     S = 4 if dna else 20
     if theta is None:
         theta = (0.002 if dna else 0.02)*divergence
@@ -196,6 +222,10 @@ def make_dataset(nloci, sites, taxa=4, model="jc69", rate_cats=1, alpha=0.5, the
     elif model == "gtr":
         freqs = np.array([0.3, 0.2, 0.2, 0.3]) if freqs is None else np.asarray(freqs)
         exch = np.array([1, 2, 1, 0.5, 1.5, 1.0]) if exch is None else np.asarray(exch)
+    elif model in CLOSED_FORM:
+        # (K80 has equal frequencies; T92's A = T, C = G holds for the default)
+        freqs = np.full(4, 0.25) if model == "k80" else np.array([0.3, 0.2, 0.2, 0.3]) if freqs is None else np.asarray(freqs)
+        own, exch = closed_form_rates(model, float(kappa), freqs)
     else:
         if freqs is None or exch is None:
             exch, freqs = lg_model()
@@ -214,7 +244,7 @@ def make_dataset(nloci, sites, taxa=4, model="jc69", rate_cats=1, alpha=0.5, the
         seqs = [letters[st[i]].tobytes().decode() for i in range(taxa)]
         pats, w = api.compress_site_patterns(seqs, dna, model == "jc69")
         out.append(dict(seqs=pats, weights=w, left=left, right=right, times=times, root=root,
-                        states=S, rate_cats=rate_cats, model=model, freqs=freqs, exch=exch,
+                        states=S, rate_cats=rate_cats, model=model, freqs=freqs, exch=own if model in CLOSED_FORM else exch,
                         rates=rates, raw_sites=sites))
     return out
 

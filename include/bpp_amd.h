@@ -523,6 +523,21 @@ long bpa_sampler_trace_read(bpa_sampler_t *, double * rows, unsigned long max_ro
 int  bpa_sampler_set_subst_model(bpa_sampler_t *, unsigned i, const double * freqs /* 4 */, const double * qrates /* 6 */, double alpha);
 int  bpa_sampler_get_subst_model(bpa_sampler_t *, unsigned i, double * freqs, double * qrates, double * alpha);
 void bpa_sampler_set_subst_moves(bpa_sampler_t *, double ft_freqs, double ft_qrates, double ft_alpha, double alpha_a, double alpha_b);
+/* The closed-form models (BPA_DNA_MODEL_K80 .. BPA_DNA_MODEL_F84) move the entries they have: the samplers take a locus's
+   model from the locus itself (bpa_locus_create) and follow bpp_amd_priors.h's table — K80 one exchangeability and no
+   frequency, F81 the frequencies only, HKY / T92 / F84 one exchangeability and the frequencies, TN93 two and the frequencies,
+   GTR five and the frequencies.  An iteration runs as many steps of a kind as the loci's maximum; a locus whose model has
+   no such step sits it out (no proposal, no draw from its stream, no counter).  No eigensystem is made for a closed-form
+   locus: its P-matrices come from the closed forms.  bpa_sampler_set_subst_model keeps its 4 + 6 + 1 layout, the entries
+   beyond the model's count are carried untouched.  The generic sampler takes such loci with several rate categories; with
+   one category they run on the big-tree sampler (implementation = BPA_SAMPLER_BIG).
+   bpa_sampler_subst_steps: how many frequency / exchangeability steps an iteration of this set runs (0 while that move's
+   width is 0).
+   bpa_sampler_set_qrates_prior: the Dirichlet(a) prior on the exchangeabilities (a00_qrates_prior_lnratio), for every model;
+   default all ones (flat: the trajectories the samplers always had, to the bit), the program's values are {2,4,2,2,4,2}
+   (locus.c:3190).  Before bpa_sampler_initialize, on a sampler that has the moves. */
+int  bpa_sampler_subst_steps(bpa_sampler_t *, unsigned * freq_steps, unsigned * qrate_steps);
+int  bpa_sampler_set_qrates_prior(bpa_sampler_t *, const double a[6]);
 /* Per-locus mutation rates: BPP's 'locusrate = 1 a_mubar b_mubar a_mui iid' under the strict clock — mu_i ~ gamma(a_mui,
    a_mui/mubar) per locus around a mean mubar ~ gamma(a_mubar, b_mubar) (the conditional-iid, "hierarchical" prior).  Every
    branch length the sampler writes or uses is (t_parent - t_child) mu_i (locus.c:2350); the MSC density does not see the

@@ -439,6 +439,22 @@ int            a00_get_subst_model(const a00_driver_t *, unsigned i, double * fr
 /* window widths (0 = that move is off; all off by default) and the gamma(a, b) prior on alpha ('alphaprior = a b ncat') */
 void           a00_set_subst_moves(a00_driver_t *, double ft_freqs, double ft_qrates, double ft_alpha, double alpha_a, double alpha_b);
 int            a00_backend_hip_params(void * ctx /* a00_hip_ctx_t* */, unsigned locus, int which, const double * values, unsigned n);
+/* The model of locus i's moves (BPA_DNA_MODEL_K80 .. BPA_DNA_MODEL_GTR of bpp_amd.h; default GTR: a driver that never
+   calls this moves three frequencies and five exchangeabilities per locus as it always did).  The closed-form models move
+   the entries they have (bpp_amd_priors.h: a00_subst_steps / a00_subst_entry / a00_subst_ref): K80 one exchangeability and
+   no frequency, F81 the frequencies only, HKY / T92 / F84 one exchangeability and the frequencies, TN93 two and the
+   frequencies.  An iteration runs as many steps of a kind as the loci's maximum; a locus whose model has no such step sits
+   it out — no proposal, no draw from its stream, no counter.  The entries beyond a model's count are carried untouched. */
+int            a00_set_subst_kind(a00_driver_t *, unsigned i, int model);
+/* The Dirichlet(a) prior on the exchangeabilities (a00_qrates_prior_lnratio of bpp_amd_priors.h), for every model.  Default:
+   all ones — a flat prior, the trajectories the driver always had; the program's values are {2,4,2,2,4,2} (locus.c:3190). */
+int            a00_set_qrates_prior(a00_driver_t *, const double a[6]);
+/* bpp_amd_priors.h's expressions as compiled, for a caller without a C compiler: the prior's term of a move of entry j from
+   qj_old to qj_new against the reference entry; the step table — the entry step `step` of kind `which` (1 frequencies, 2
+   exchangeabilities) moves for `model` (-1: none), its reference entry, the number of steps; returns the model's number of
+   exchangeability entries */
+double         a00_qrates_prior_piece(const double a[6], int j, int ref, double qj_old, double qj_new, double qref_old, double qref_new);
+int            a00_subst_table(int model, int which, int step, int * entry, int * ref, int * steps);
 
 /* ---- per-locus mutation rates: BPP's 'locusrate = 1 a_mubar b_mubar a_mui iid' under the strict clock (the conditional-iid,
    "hierarchical" prior: mu_i ~ gamma(a_mui, a_mui/mubar), mubar ~ gamma(a_mubar, b_mubar)).  Every branch length handed to the

@@ -50,4 +50,50 @@ static inline A00_HD double a00_theta_lnacc_kind(int kind, long k, double T, dou
   return a00_theta_lnacc(k, T, told, tnew, a, b);
 }
 
+/* ---- the substitution-parameter moves by model (a00_set_subst_kind; the device samplers read the locus's own model).
+   `model` is BPA_DNA_MODEL_* (bpp_amd.h: 0 JC69, 1 K80, 2 F81, 3 HKY, 4 T92, 5 TN93, 6 F84, 7 GTR; anything above, the
+   device's 100 for "eigendecomposition" included, moves as GTR).  One statement for the host driver and the device kernels.
+     exchangeability entries   K80, HKY, T92, F84: 2   TN93: 3   GTR: 6   JC69, F81: none          locus.c:906-952
+     their reference entry     TN93: 2   every other model: 1 (GTR: the A<->G rate)               locus.c:3197-3229
+     frequencies               JC69, K80: none   every other model: 0, 1, 2 against T (entry 3)   locus.c:2782-2791
+   Step s of a kind proposes the locus's s-th moving entry (GTR: 0, 2, 3, 4, 5 — the order the moves always had); a locus
+   whose model has fewer sits the step out.                                                                                 */
+static inline A00_HD int a00_subst_qrates(int model)
+{
+  return model >= 7 ? 6 : model == 5 ? 3 : (model == 0 || model == 2) ? 0 : 2;
+}
+static inline A00_HD int a00_subst_ref(int which /* 1 frequencies, 2 exchangeabilities */, int model)
+{
+  return which == 1 ? 3 : model == 5 ? 2 : 1;
+}
+static inline A00_HD int a00_subst_steps(int which, int model)
+{
+  if (which == 1) return (model == 0 || model == 1) ? 0 : 3;
+  return a00_subst_qrates(model) > 0 ? a00_subst_qrates(model) - 1 : 0;
+}
+/* the entry step s moves, -1: this model has no such step */
+static inline A00_HD int a00_subst_entry(int which, int model, int s)
+{
+  if (s < 0 || s >= a00_subst_steps(which, model)) return -1;
+  return (which == 2 && s >= a00_subst_ref(2, model)) ? s + 1 : s;
+}
+/* the Dirichlet(a) prior on a model's exchangeabilities in the move of entry j against the reference entry: what joins
+   (log q_j' - log q_j) in the Hastings term,
+     (a_j - 1)(log q_j' - log q_j) + (a_ref - 1) log(q_ref'/q_ref)                              locus.c:3190, 3301-3304
+   for every model, indexed by j and ref; the program's a is {2,4,2,2,4,2}.  A term whose a is 1 is not formed (as in the
+   reference), so a prior of ones leaves the Hastings term what it was, to the bit.                                        */
+static inline A00_HD double a00_qrates_prior_lnratio(const double * a, int j, int ref, double lj_old, double lj_new, double ref_old, double ref_new)
+{
+  double r = 0;
+  if (a[j] - 1 != 0) r += (a[j] - 1.0)*(lj_new - lj_old);
+  if (a[ref] - 1 != 0) r += (a[ref] - 1.0)*log(ref_new/ref_old);
+  return r;
+}
+static inline A00_HD int a00_qrates_prior_flat(const double * a)
+{
+  int q, flat = 1;
+  for (q = 0; q < 6; ++q) flat = flat && a[q] == 1.0;
+  return flat;
+}
+
 #endif
