@@ -3776,7 +3776,7 @@ __global__ void __launch_bounds__(64) params_install_kernel(const LocusDev * loc
   if (which == 4u) { for (uint32_t k = 0; k < R; ++k) L.par[par_rates(R) + k] = v[k]; return; }
   if (which == 1u) for (uint32_t i = 0; i < S; ++i) pm[pm_freqs(S) + i] = v[i];
   if (which == 2u) for (uint32_t i = 0; i < S*(S-1)/2; ++i) pm[pm_subst(S) + i] = v[i];
-  if (L.model == 0) return;                       // JC69: no eigensystem
+  if (L.model == 0 || (S == 4 && L.model <= 6)) return;     // JC69 and the closed-form DNA models (K7): no eigensystem
   if (SK == 4 || (SK == 0 && S == 4)) update_eigen_regs<4>(pm + pm_freqs(4), pm + pm_subst(4), pm + pm_evals(4), pm + pm_evecs(4), pm + pm_ievecs(4));
   else                                update_eigen_dev<20>(pm + pm_freqs(20), pm + pm_subst(20), pm + pm_evals(20), pm + pm_evecs(20), pm + pm_ievecs(20));
 }

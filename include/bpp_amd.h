@@ -250,7 +250,9 @@ int          bpa_plan_get_sum(bpa_plan_t *, double * sum);
    locus), 2 substitution parameters (states(states-1)/2), 4 category rates (rate_cats); values packed
    [locus of the plan][value].  ONE transfer (or none: the _device form takes device memory), one kernel that
    installs them and refreshes the touched eigensystems on the device (K6, pll_update_eigen).  The next launch
-   of a plan that updates all matrices and partials then evaluates the proposal.                            */
+   of a plan that updates all matrices and partials then evaluates the proposal.  JC69 loci and loci of the
+   closed-form DNA models (K80 .. F84) have no eigensystem: their values are installed and nothing else of
+   their parameter block is written.                                                                         */
 /* a caller-side tape resident in HBM: copy `bytes` from the host into device memory owned by the engine (freed
    with it) and return the device address, e.g. the value arrays bpa_plan_set_params_device reads            */
 void *       bpa_engine_stage(bpa_engine_t *, const void * host, size_t bytes);

@@ -3,7 +3,9 @@
 the table of include/bpp_amd_priors.h), no eigen work for them, the Dirichlet prior on the exchangeabilities
 (bpa_sampler_set_qrates_prior) — decision by decision against the C host driver on the same library, the step counts, the
 state after a long run against a CPU recompute, GTR with the default prior, and what is refused.
-CPU twin: tests/test_closedform_host.py; helpers: tests/closedform.py."""
+CPU twin: tests/test_closedform_host.py; helpers: tests/closedform.py.  The same models at the edges of their parameters — frequencies
+and entries at the moves' floor, kappa from 5e-13 to 2e12, every batched route of the plans, the moves at both ends of their
+reflection: tests/test_gpu_closedform_edges.py, tests/test_closedform_edges_host.py, tests/k7.py."""
 import numpy as np
 import pytest
 
@@ -36,6 +38,12 @@ def case(name):
         # K80+Gamma2 / HKY+Gamma4 / TN93+Gamma4 / GTR+Gamma4, two loci each, 8 tips, 28 .. 32 patterns
         base = shapes.shaped_set(list(range(8)), st8, [28 + k % 5 for k in range(8)], 132, model="gtr", rate_cats=4)
         models, cats = ["k80", "k80", "hky", "hky", "tn93", "tn93", "gtr", "gtr"], [2, 2, 4, 4, 4, 4, 4, 4]
+        c = dict(data=[CF.recat(d, r) for d, r in zip(CF.with_model(base, models), cats)], species=None, stree=st8, impl=None)
+    elif name == "gen-rest":
+        # the models the two sets above lack, every locus with several categories (one generic part, no composite):
+        # F81+Gamma4 / T92+Gamma4 / F84+Gamma4 / F84+Gamma2, two loci each, 8 tips, 28 .. 32 patterns
+        base = shapes.shaped_set(list(range(8)), st8, [28 + k % 5 for k in range(8)], 137, model="gtr", rate_cats=4)
+        models, cats = ["f81", "f81", "t92", "t92", "f84", "f84", "f84", "f84"], [4, 4, 4, 4, 4, 4, 2, 2]
         c = dict(data=[CF.recat(d, r) for d, r in zip(CF.with_model(base, models), cats)], species=None, stree=st8, impl=None)
     elif name == "big-17":
         # 6 loci x 17 tips: HKY with ONE category, HKY+Gamma4, TN93+Gamma4, GTR+Gamma4, K80+Gamma2, F84 with one category
@@ -75,6 +83,10 @@ GENERIC = [
     ("gen-mixed", "uniform", {}),
     ("gen-mixed", "program", {}),
     ("gen-mixed", "program", dict(host_decisions=True)),
+    ("gen-rest", "uniform", {}),                               # F81, T92, F84 (kappa = q0/q1): the model == 2, 4, 6 branches of gstep2_kernel
+    ("gen-rest", "program", {}),
+    ("gen-rest", "program", dict(host_decisions=True)),
+    ("gen-rest", "uniform", dict(chain=True)),
 ]
 BIG = [("big-17", "uniform"), ("big-17", "program"), ("big-8-f81", "uniform"), ("big-8-f81", "program"),
        ("big-8-t92", "uniform"), ("big-8-t92", "program")]
@@ -181,7 +193,7 @@ def one_iteration(c, on, models=None):
     return steps, s["proposals"], s["launches"]
 
 
-@pytest.mark.parametrize("name", ["gen-hky", "gen-mixed", "big-17", "big-8-f81"])
+@pytest.mark.parametrize("name", ["gen-hky", "gen-mixed", "gen-rest", "big-17", "big-8-f81"])
 def test_step_counts_equal_the_table(name):
     """subst_steps() and the proposals of an iteration are the table's (HKY: 3 + 1 steps, 5 proposals a locus with Gamma; the
     parent ran 9 steps); the moves off: no steps.  On the all-HKY set declared GTR instead, the iteration has four more steps,
@@ -201,7 +213,7 @@ def test_step_counts_equal_the_table(name):
 
 
 # ------------------------------------------------------------------ 3. the state after a long run
-@pytest.mark.parametrize("name,moves", [("gen-mixed", "uniform"), ("gen-mixed", "program"), ("big-17", "uniform"), ("big-17", "program")])
+@pytest.mark.parametrize("name,moves", [("gen-mixed", "uniform"), ("gen-mixed", "program"), ("gen-rest", "program"), ("big-17", "uniform"), ("big-17", "program")])
 def test_state_after_300_iterations(name, moves):
     """300 iterations in one call, then invariants.check_state: trees, populations, densities, every lnL against the oracle at
     the current parameters (1e-10), and every device buffer — P-matrices against the oracle's closed form (eigen form for the
