@@ -18,14 +18,14 @@
 // that cannot be made (draw_window / skip_u / accept of a00_driver.c).  It runs with the program's THETA / TAU / MIX
 // (bpa_sampler_set_program_moves): TAU's window variate and MIX's factor come from the decisions' state on the device
 // (gsm::GDecState), a locus brings its Jacobian and TAU's three T2h, and gsm::gdec_kernel decides from the sums
-// (bigsampler_host.hpp: gb_iterate).  big_step_kernel<false> is the uniform-window step as it has always been.
+// (gsampler_host.hpp: gs_iterate).  big_step_kernel<false> is the uniform-window step as it has always been.
 //
 // Per-locus scalars, with the generic sampler's contract (gsampler.hpp: GArgs) and the host driver's code (mui_step / hered_step /
 // a00_iterate of a00_driver.c), in both instantiations: a locus's heredity scalar h_i enters tree_logpr (h_i theta_p first; the
 // T2h it leaves for THETA and TAU stay unscaled, the sum kernels divide by h_i), its rate mu_i every branch length of the records.
 // Mode 9, MUI: sliding window on log mu_i from the locus's stream, every branch and every inner node evaluated again, settled
 // as pend 4 (no density term, own counters, the old rate back on rejection).  Mode 10, HRDT: h' = |h + ft_h w|, the stored tree's
-// density at h', decided inside the launch, nothing pending.  MUBAR is gsm::gmubar_kernel (bigsampler_host.hpp: gb_mubar).  Null
+// density at h', decided inside the launch, nothing pending.  MUBAR is gsm::gmubar_kernel (gsampler_host.hpp: gs_mubar).  Null
 // rate / scalar arrays are "all 1, no load": a sampler that never set any walks the trajectory it always did, to the bit.
 //
 //

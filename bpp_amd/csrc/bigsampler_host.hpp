@@ -1,10 +1,11 @@
-// bigsampler_host.hpp — host side of the big-tree device sampler (bigsampler.hpp): uploads, the launch loop of an iteration,
-// downloads.  Included at the end of sampler.hpp, after gsampler_host.hpp (whose buffers and all-loci kernels it shares).
+// bigsampler_host.hpp — host side of the big-tree device sampler (bigsampler.hpp), what is its own: the upload, one step launch
+// (gb_step), one evaluation (gb_eval), the head of the download.  The launch loop of an iteration is the generic sampler's
+// (gsampler_host.hpp: gs_iterate), which reaches the two launches through sampler_step / sampler_eval, defined below.
+// Included at the end of sampler.hpp, after gsampler_host.hpp (whose buffers and all-loci kernels it shares).
 #pragma once
 
 // the substitution-parameter moves' tables (gs_subst_ready: the generic sampler's, with its refusals) and the loci's bytes for
 // big_par_kernel, made when a window width first becomes positive: a sampler that never set one has none of them
-static bool gb_subst_moves(const bpa_sampler * s) { return s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0; }
 static int gb_subst_ready(bpa_sampler * s)
 {
   if (!gs_subst_ready(s)) return 0;
@@ -156,138 +157,14 @@ static int gb_eval(bpa_sampler * s, int kind)
   return 1;
 }
 
-static int gb_decide(bpa_sampler * s, double uacc, int tau_q, double win_u, double mix_c, double mix_lnc)
+// the two leaves of the launch loop both samplers share (declared in sampler.hpp; gs_iterate, gs_dev_allloci, gs_mubar)
+static inline int sampler_step(bpa_sampler * s, unsigned mode, unsigned k, double tau_u, double mix_c, double mix_lnc)
 {
-  bpa_engine * e = s->eng;
-  s->epoch++;
-  hipLaunchKernelGGL(gsm::gsum_decide_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, s->g_lnl.p, s->g_delta.p,
-                     s->g_active.p, s->nloci, (double *)nullptr, 1, uacc, s->epoch, s->flag.p, s->counters.p, s->taus.p, s->sp, tau_q, win_u, mix_c, mix_lnc);
-  HIPCHK(hipGetLastError());
-  s->launches++;
-  return 1;
+  return s->big ? gb_step(s, mode, k, tau_u, mix_c, mix_lnc) : gs_step(s, mode, k, tau_u, mix_c, mix_lnc);
 }
+static inline int sampler_eval(bpa_sampler * s, int kind) { return s->big ? gb_eval(s, kind) : gs_eval(s, kind); }
 
 static int gb_initialize(bpa_sampler * s) { return gb_step(s, 5) && gb_eval(s, 1); }
-
-// an all-loci step of the program's moves, decided on the device (gs_dev_allloci of gsampler_host.hpp with this sampler's
-// step and evaluation): proposal from the decisions' state, likelihood, the loci's sums, gdec_kernel — nothing waits for the host
-static int gb_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
-{
-  bpa_engine * e = s->eng;
-  const bool mix = q < 0;
-  if (!gb_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !gb_eval(s, 1)) return 0;
-  hipLaunchKernelGGL(gsm::gdec_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
-                     (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p, (const double *)s->g_hered.p);
-  HIPCHK(hipGetLastError());
-  s->launches++;
-  s->epoch++;
-  s->logpr_stale = true;             // (an accepted step re-drew thetas; the host does not know the decision: every density is taken again)
-  return mix ? gs_dec_launch<2>(s, -1, -1) : gs_dec_launch<1>(s, q, q + 1);
-}
-
-// MUBAR (gs_mubar of gsampler_host.hpp; mubar_step of a00_driver.c): the pending rate step is settled first (the sum must see the
-// rates the loci kept), then ONE launch sums and decides — with the host's two numbers (uniform windows) or from the decisions'
-// state on the device (the program's moves: the two draws follow MIX's in the global stream, where a00_iterate puts them)
-static int gb_mubar(bpa_sampler * s)
-{
-  bpa_engine * e = s->eng;
-  if (!gb_step(s, 4)) return 0;
-  const double ft = s->g_lr_ft[1], am = s->g_a_mui, a = s->g_a_mubar, b = s->g_b_mubar;
-  if (!s->kernel_bpp)
-  {
-    const double w = a00_rndu(&s->grng) - 0.5, u = a00_rndu(&s->grng);
-    hipLaunchKernelGGL((gsm::gmubar_kernel<0>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, w, u);
-  }
-  else
-    hipLaunchKernelGGL((gsm::gmubar_kernel<1>), dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, &s->g_dst.p->z, ft, am, a, b, 0.0, 0.0);
-  HIPCHK(hipGetLastError());
-  s->launches++;
-  return 1;
-}
-
-// the tail of an iteration, in a00_iterate's order: the heredity scalars after MIX (method.c:5616-5621; one launch that settles
-// MIX, proposes and decides), then the loci's rates with their evaluation and the rates' mean (method.c:5745-5773).  With a fixed
-// mean MUI closes the iteration: the next launch — the next iteration's first, or the download's — settles it.  Between the
-// two, the substitution-parameter moves (method.c:5699-5735; param_step of a00_driver.c, gs_iterate's order): the three
-// frequencies, the five exchangeabilities, alpha, each a step of all loci with its evaluation; with the rate moves off the
-// last of them closes the iteration in the same way
-static int gb_scalars(bpa_sampler * s)
-{
-  if (s->g_h_ft > 0) { if (!gb_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
-  unsigned nfreq = 0, nqr = 0;
-  subst_step_counts(s, &nfreq, &nqr);
-  for (unsigned j = 0; j < nfreq; ++j) { if (!gb_step(s, 6, j) || !gb_eval(s, 0)) return 0; }
-  for (unsigned j = 0; j < nqr; ++j)   { if (!gb_step(s, 7, j) || !gb_eval(s, 0)) return 0; }
-  if (s->g_ft[2] > 0)                                   { if (!gb_step(s, 8, 0) || !gb_eval(s, 0)) return 0; }
-  if (gb_subst_moves(s))
-    for (bpa_locus * l : s->loci) l->host_par_stale = true;              // the device blocks moved ahead of the host mirrors
-  if (s->g_lr_ft[0] > 0) { if (!gb_step(s, 9) || !gb_eval(s, 0)) return 0; }
-  if (s->g_lr_ft[1] > 0 && (s->g_a_mubar > 0 || s->g_b_mubar > 0)) { if (!gb_mubar(s)) return 0; }
-  return 1;
-}
-
-static int gb_iterate(bpa_sampler * s, unsigned iterations)
-{
-  bpa_engine * e = s->eng;
-  if (gs_lr_moves(s) && !(s->g_a_mui > 0)) return fail("bpa_sampler: the locus-rate moves need a_mui > 0");
-  if (s->g_h_ft > 0 && !(s->g_h_a > 0 && s->g_h_b > 0)) return fail("bpa_sampler: the heredity move needs a, b > 0");
-  if (gb_subst_moves(s) && (s->allreduce || s->p2p)) return fail("bpa_sampler: the big-tree sampler's substitution-parameter moves run on one rank");
-  if (s->g_ft[2] > 0 && s->g_rmax > 8) return fail("bpa_sampler: the alpha move takes loci of up to 8 rate categories");
-  if (!gs_lr_ready(s) || !gs_hered_ready(s) || !gb_subst_ready(s)) return 0;
-  s->host_current = false;
-  const bool prog = gs_prog(s);
-  if (s->kernel_bpp && !prog) return fail("bpa_sampler: on the big-tree sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
-  if (prog && !gs_prog_ready(s)) return 0;
-  // the sample trace: on a row's iteration the step that closes it is settled and the row read from the trees behind it
-  auto rowlog_row = [&]() {
-    return !rowlog_tick(s) || (gb_step(s, 4) &&
-           rowlog_emit(s, reinterpret_cast<const char *>(s->b_dev.p) + offsetof(gbig::BTree, lnl), sizeof(gbig::BTree), nullptr));
-  };
-  for (unsigned it = 0; it < iterations; ++it)
-  {
-    const unsigned ngage = s->maxtips - 1, ngspr = 2*s->maxtips - 2;
-    for (unsigned k = 0; k < ngage; ++k)   { if (!gb_step(s, 0, k) || !gb_eval(s, 0)) return 0; }
-    for (unsigned k = 0; k < ngspr; ++k)   { if (!gb_step(s, 1, k) || !gb_eval(s, 0)) return 0; }
-    s->sweeps++;
-    if (prog)
-    {
-      // THETA / TAU / MIX as the program runs them (gs_iterate's device-decided branch): the host is paced two iterations behind
-      // its own launches and waits for nothing else
-      if (s->gp_pace_n >= 2) HIPCHK(hipEventSynchronize(s->gp_pace[(s->gp_pace_n - 2) & 3u]));
-      if (!gb_step(s, 4) || !gs_dev_theta(s)) return 0;
-      for (int q = s->sp.S; q < s->sp.npop; ++q) if (!gb_dev_allloci(s, q)) return 0;
-      if (!gb_dev_allloci(s, -1)) return 0;
-      hipEvent_t & ev = s->gp_pace[s->gp_pace_n & 3u];
-      if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      HIPCHK(hipEventRecord(ev, e->stream));
-      s->gp_pace_n++;
-      if (!gb_scalars(s) || !rowlog_row()) return 0;
-      continue;
-    }
-    if (s->sp.theta_alpha > 0)
-    {
-      if (!gb_step(s, 4)) return 0;
-      smp::ThetaArgs ta{};
-      for (int p = 0; p < s->sp.npop; ++p)
-        if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
-      hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                         s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)s->g_hered.p);
-      HIPCHK(hipGetLastError());
-      s->logpr_stale = true;
-      s->launches += 1;
-    }
-    for (int q = s->sp.S; q < s->sp.npop; ++q)
-    {
-      const double uprop = a00_rndu(&s->grng), uacc_t = a00_rndu(&s->grng);
-      if (!gb_step(s, 2, (unsigned)q, uprop) || !gb_eval(s, 1) || !gb_decide(s, uacc_t, q, uprop, 1.0, 0.0)) return 0;
-    }
-    const double lnc = s->sp.ft_mix*(a00_rndu(&s->grng) - 0.5), c = std::exp(lnc);
-    const double uacc = a00_rndu(&s->grng);
-    if (!gb_step(s, 3, 0, 0.0, c, lnc) || !gb_eval(s, 1) || !gb_decide(s, uacc, -1, 0.0, c, lnc)) return 0;
-    if (!gb_scalars(s) || !rowlog_row()) return 0;
-  }
-  return 1;
-}
 
 static int gb_download(bpa_sampler * s)
 {
@@ -296,14 +173,5 @@ static int gb_download(bpa_sampler * s)
   //  are level with the settled values before a plan or bpa_batch_evaluate computes from them)
   if (!gb_step(s, 4) || !gs_prog_pull(s)) return 0;
   HIPCHK(hipMemcpyAsync(s->b_trees.data(), s->b_dev.p, s->nloci*sizeof(gbig::BTree), hipMemcpyDeviceToHost, e->stream));
-  if (s->g_sm.p && !s->g_sm_host.empty())
-    HIPCHK(hipMemcpyAsync(s->g_sm_host.data(), s->g_sm.p, s->g_sm_host.size()*sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  if (s->g_mui.p)
-  {
-    HIPCHK(hipMemcpyAsync(s->g_mui_host.data(), s->g_mui.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(&s->g_lr_host, s->g_lr.p, sizeof(gsm::GLrState), hipMemcpyDeviceToHost, e->stream));
-  }
-  if (s->g_hered.p) HIPCHK(hipMemcpyAsync(s->g_hered_host.data(), s->g_hered.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return 1;
+  return gs_download_tail(s);
 }

@@ -5,9 +5,10 @@
 // the substitution-parameter moves' device tables (every locus's frequencies | exchangeabilities | alpha, the roll-back
 // pairs, the loci's ids): made when a window width first becomes positive — the widths themselves travel with every
 // launch, so switching a move on or changing a width in mid-run (BPP's burn-in finetune adjustment) touches no state
+static bool gs_subst_moves(const bpa_sampler * s) { return s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0; }
 static int gs_subst_ready(bpa_sampler * s)
 {
-  if (!(s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0) || s->g_sm.p) return 1;
+  if (!gs_subst_moves(s) || s->g_sm.p) return 1;
   const unsigned T = s->nloci;
   // (the big-tree sampler takes loci of any 4-state model side by side: one without an eigendecomposition among them refuses
   //  the moves; a locus with ONE rate category runs there — its alpha step proposes nothing, a00_driver.c:1187)
@@ -668,9 +669,11 @@ static int gs_eval(bpa_sampler * s, int kind /* 0 per-locus step, 1 all-loci ste
 // Default: small JC69 sets only — up to 1 024 loci of at most 64 patterns on average (config 5: 913 -> 1 096 it/s).  With
 // several rate categories or hundreds of patterns a wave per locus walking one pattern per lane loses to the packing's
 // kernels even when those are launch-bound (config 3's share of 1 250 loci: 516 it/s by launches, 337 chained).
+// Never on the big-tree sampler, which shares the launch loop: gchain_kernel walks the generic sampler's trees (g_dev), and
+// the big-tree sampler has none (its g_alljc is still the default, its sets are small: the test below would say yes).
 static bool gs_chain_wanted(const bpa_sampler * s)
 {
-  if (s->g_s20 || !s->eng->usedata || s->maxtips < 2) return false;
+  if (s->big || s->g_s20 || !s->eng->usedata || s->maxtips < 2) return false;
   if (s->opt.chain >= 0) return s->opt.chain != 0;
   return s->g_alljc && s->nloci <= 1024u && s->g_npat <= 64u*s->nloci;
 }
@@ -1133,11 +1136,13 @@ static int gs_dev_theta(bpa_sampler * s)
   if (!gs_dev_allreduce(s, 4u*(unsigned)s->sp.npop)) return 0;
   return gs_dec_launch<0>(s, -1, s->sp.S);
 }
+// an all-loci step (TAU of population q, or MIX) of either sampler: proposal from the decisions' state, likelihood, the loci's
+// sums, gdec_kernel — nothing waits for the host
 static int gs_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
 {
   bpa_engine * e = s->eng;
   const bool mix = q < 0;
-  if (!gs_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !gs_eval(s, 1)) return 0;
+  if (!sampler_step(s, mix ? 3u : 2u, mix ? 0u : (unsigned)q) || !sampler_eval(s, 1)) return 0;
   hipLaunchKernelGGL(gsm::gdec_sums_kernel, dim3(1), dim3(1024), 0, e->stream, (const double *)s->g_lnlcur.p, (const double *)s->g_lnl.p, (const double *)s->g_delta.p,
                      (const uint8_t *)s->g_active.p, (const double *)s->g_t2h3.p, s->nloci, mix ? 0 : 1, s->g_dsum.p, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
@@ -1156,7 +1161,7 @@ static int gs_dev_allloci(bpa_sampler * s, int q /* -1: MIX */)
 static int gs_mubar(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
-  if (!gs_step(s, 4)) return 0;
+  if (!sampler_step(s, 4)) return 0;
   const double ft = s->g_lr_ft[1], am = s->g_a_mui, a = s->g_a_mubar, b = s->g_b_mubar;
   if (!s->kernel_bpp)
   {
@@ -1187,17 +1192,32 @@ static int gs_mubar(bpa_sampler * s)
   return 1;
 }
 
+// where the sample trace reads the loci's lnl: the first tree's, and the stride to the next
+static const char * gs_trace_lnl(const bpa_sampler * s, size_t * stride)
+{
+  *stride = s->big ? sizeof(gbig::BTree) : sizeof(gsm::GTree);
+  return s->big ? reinterpret_cast<const char *>(s->b_dev.p) + offsetof(gbig::BTree, lnl)
+                : reinterpret_cast<const char *>(s->g_dev.p) + offsetof(gsm::GTree, lnl);
+}
+
+// an iteration's launches, for the generic and for the big-tree sampler: sampler_step / sampler_eval launch either one's
+// kernels, everything else — the order of the steps, the draws from the global stream, the all-loci kernels — is the same code.
+// Every refusal comes before the first launch.  What a big-tree sampler never reaches: the chain launch (gs_chain_wanted), the
+// all-reduce branches (gb_upload refuses a callback), the host-decided program moves (gs_prog_dev_wanted), the fork (gs_join)
 static int gs_iterate(bpa_sampler * s, unsigned iterations)
 {
   bpa_engine * e = s->eng;
-  if (!gs_subst_ready(s)) return 0;
   if (gs_lr_moves(s) && !(s->g_a_mui > 0)) return fail("bpa_sampler: the locus-rate moves need a_mui > 0");
-  if (!gs_lr_ready(s)) return 0;
   if (s->g_h_ft > 0 && !(s->g_h_a > 0 && s->g_h_b > 0)) return fail("bpa_sampler: the heredity move needs a, b > 0");
-  if (!gs_hered_ready(s)) return 0;
+  if (s->big && gs_subst_moves(s) && (s->allreduce || s->p2p)) return fail("bpa_sampler: the big-tree sampler's substitution-parameter moves run on one rank");
+  if (s->big && s->g_ft[2] > 0 && s->g_rmax > 8) return fail("bpa_sampler: the alpha move takes loci of up to 8 rate categories");
+  // (the arrays of the moves that are on: allocations only — and the refusals of the substitution-parameter moves' tables)
+  if (!gs_lr_ready(s) || !gs_hered_ready(s) || !(s->big ? gb_subst_ready(s) : gs_subst_ready(s))) return 0;
   s->host_current = false;
   const bool prog = gs_prog(s);
-  if (s->kernel_bpp && !prog) return fail("bpa_sampler: on a generic sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
+  if (s->kernel_bpp && !prog)
+    return fail(s->big ? "bpa_sampler: on the big-tree sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior"
+                       : "bpa_sampler: on a generic sampler BPP's proposal kernel comes with the program's moves (bpa_sampler_set_program_moves) and a theta prior");
   if (prog && !gs_prog_ready(s)) return 0;
   for (unsigned it = 0; it < iterations; ++it)
   {
@@ -1206,8 +1226,8 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
     if (gs_chain_wanted(s)) { if (!gs_chain(s)) return 0; }
     else
     {
-      for (unsigned k = 0; k + 1 < s->maxtips; ++k)     { if (!gs_step(s, 0, k) || !gs_eval(s, 0)) return 0; }
-      for (unsigned k = 0; k + 2 < 2*s->maxtips; ++k)   { if (!gs_step(s, 1, k) || !gs_eval(s, 0)) return 0; }
+      for (unsigned k = 0; k + 1 < s->maxtips; ++k)     { if (!sampler_step(s, 0, k) || !sampler_eval(s, 0)) return 0; }
+      for (unsigned k = 0; k + 2 < 2*s->maxtips; ++k)   { if (!sampler_step(s, 1, k) || !sampler_eval(s, 0)) return 0; }
     }
     s->sweeps++;
     if (prog)
@@ -1222,7 +1242,7 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
         // instead: before an iteration's all-loci steps it waits for the END of the iteration before the last — work the GPU
         // finished long ago unless the host is the faster of the two; no decision depends on this wait.
         if (s->gp_pace_n >= 2) HIPCHK(hipEventSynchronize(s->gp_pace[(s->gp_pace_n - 2) & 3u]));
-        if (!gs_step(s, 4) || !gs_dev_theta(s)) return 0;
+        if (!sampler_step(s, 4) || !gs_dev_theta(s)) return 0;
         for (int q = s->sp.S; q < s->sp.npop; ++q) if (!gs_dev_allloci(s, q)) return 0;
         if (!gs_dev_allloci(s, -1)) return 0;
         hipEvent_t & ev = s->gp_pace[s->gp_pace_n & 3u];
@@ -1230,7 +1250,7 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
         HIPCHK(hipEventRecord(ev, e->stream));
         s->gp_pace_n++;
       }
-      else
+      else           // (host_decisions: a generic sampler only, gs_prog_dev_wanted)
       {
       if (any) { unsigned int gz = (unsigned int)s->grng; s->gp_pre_window = a00_bpp_rnd_symmetrical(&gz); s->gp_pre_valid = true; s->grng = (a00_rng_t)gz; }
       if (!gs_step(s, 4) || !gs_prog_theta(s)) return 0;
@@ -1240,60 +1260,43 @@ static int gs_iterate(bpa_sampler * s, unsigned iterations)
     }
     else
     {
-    if (s->sp.theta_alpha > 0)
-    {
-      // settle the last per-locus step and leave the statistics of every tree's density; then THETA as in the sweep path
-      if (!gs_step(s, 4)) return 0;
-      smp::ThetaArgs ta{};
-      for (int p = 0; p < s->sp.npop; ++p)
-        if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
-      if (!s->allreduce)
-        hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)s->g_hered.p);
-      else
-      {
-        hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0, (const double *)s->g_hered.p);
-        double * ar = s->sum_ext ? s->sum_ext : s->theta_sums.p;
-        const size_t nb = (size_t)s->sp.npop*sizeof(double);
-        if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(ar, s->theta_sums.p, nb, hipMemcpyDeviceToDevice, e->stream));
-        if (!s->allreduce(s->allreduce_ctx, ar, (unsigned)s->sp.npop, (void *)e->stream)) return fail("bpa_sampler: the all-reduce callback failed");
-        if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(s->theta_sums.p, ar, nb, hipMemcpyDeviceToDevice, e->stream));
-        hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1, (const double *)s->g_hered.p);
-      }
-      HIPCHK(hipGetLastError());
-      s->logpr_stale = true;
-      s->launches += 1;
-    }
+    // settle the last per-locus step and leave the statistics of every tree's density; then THETA as in the sweep path
+    if (s->sp.theta_alpha > 0 && (!sampler_step(s, 4) || !theta_uniform_step(s, s->g_hered.p))) return 0;
     for (int q = s->sp.S; q < s->sp.npop; ++q)                    // one rubber-band step per species divergence
     {
       const double uprop = a00_rndu(&s->grng), uacc_t = a00_rndu(&s->grng);
-      if (!gs_step(s, 2, (unsigned)q, uprop) || !gs_eval(s, 1) || !gs_decide(s, uacc_t, q, uprop, 1.0, 0.0)) return 0;
+      if (!sampler_step(s, 2, (unsigned)q, uprop) || !sampler_eval(s, 1) || !gs_decide(s, uacc_t, q, uprop, 1.0, 0.0)) return 0;
     }
     const double lnc = s->sp.ft_mix*(a00_rndu(&s->grng) - 0.5), c = std::exp(lnc);
     const double uacc = a00_rndu(&s->grng);
-    if (!gs_step(s, 3, 0, 0.0, c, lnc) || !gs_eval(s, 1) || !gs_decide(s, uacc, -1, 0.0, c, lnc)) return 0;
+    if (!sampler_step(s, 3, 0, 0.0, c, lnc) || !sampler_eval(s, 1) || !gs_decide(s, uacc, -1, 0.0, c, lnc)) return 0;
     }
-    // the heredity scalars after MIX, before the substitution parameters (method.c:5616-5621; hered_step of a00_driver.c): one
-    // launch per part-batch that settles MIX, proposes and decides — no evaluation, nothing pending afterwards
-    if (s->g_h_ft > 0) { if (!gs_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
-    // the substitution-parameter moves come last (method.c:5699-5735; param_step of a00_driver.c)
+    // the tail of an iteration, in a00_iterate's order.  The heredity scalars after MIX, before the substitution parameters
+    // (method.c:5616-5621; hered_step of a00_driver.c): one launch (per part-batch) that settles MIX, proposes and decides —
+    // no evaluation, nothing pending afterwards
+    if (s->g_h_ft > 0) { if (!sampler_step(s, 10)) return 0; s->g_h_prop += s->nloci; }
+    // the substitution-parameter moves (method.c:5699-5735; param_step of a00_driver.c), each a step of all loci with its evaluation
     // (as many steps of a kind as the loci's models have at most, a00_subst_steps: GTR 3 + 5, HKY 3 + 1, K80 0 + 1)
     unsigned nfreq = 0, nqr = 0;
     subst_step_counts(s, &nfreq, &nqr);
-    for (unsigned j = 0; j < nfreq; ++j) { if (!gs_step(s, 6, j) || !gs_eval(s, 0)) return 0; }
-    for (unsigned j = 0; j < nqr; ++j)   { if (!gs_step(s, 7, j) || !gs_eval(s, 0)) return 0; }
-    if (s->g_ft[2] > 0)                                   { if (!gs_step(s, 8, 0) || !gs_eval(s, 0)) return 0; }
-    if (s->g_ft[0] > 0 || s->g_ft[1] > 0 || s->g_ft[2] > 0)
+    for (unsigned j = 0; j < nfreq; ++j) { if (!sampler_step(s, 6, j) || !sampler_eval(s, 0)) return 0; }
+    for (unsigned j = 0; j < nqr; ++j)   { if (!sampler_step(s, 7, j) || !sampler_eval(s, 0)) return 0; }
+    if (s->g_ft[2] > 0)                                   { if (!sampler_step(s, 8, 0) || !sampler_eval(s, 0)) return 0; }
+    if (gs_subst_moves(s))
       for (bpa_locus * l : s->loci) l->host_par_stale = true;            // the device blocks moved ahead of the host mirrors
-    // ... then the loci's rates and their mean (method.c:5745-5773; mui_step / mubar_step of a00_driver.c)
-    if (s->g_lr_ft[0] > 0) { if (!gs_step(s, 9) || !gs_eval(s, 0)) return 0; }
+    // ... then the loci's rates and their mean (method.c:5745-5773; mui_step / mubar_step of a00_driver.c).  With a fixed mean
+    // MUI closes the iteration (with the rate moves off, the last parameter step does): the next launch — the next
+    // iteration's first, or the download's — settles it
+    if (s->g_lr_ft[0] > 0) { if (!sampler_step(s, 9) || !sampler_eval(s, 0)) return 0; }
     if (s->g_lr_ft[1] > 0 && (s->g_a_mubar > 0 || s->g_b_mubar > 0)) { if (!gs_mubar(s)) return 0; }
     // the sample trace: on a row's iteration the last step is settled (the launch joins the part-batches' streams first) and
     // the row read from the trees behind it — no levelling of the roots' buffers, nothing copied to the host
-    if (rowlog_tick(s) && (!gs_step(s, 4) ||
-        !rowlog_emit(s, reinterpret_cast<const char *>(s->g_dev.p) + offsetof(gsm::GTree, lnl), sizeof(gsm::GTree), nullptr))) return 0;
+    if (rowlog_tick(s))
+    {
+      size_t stride = 0;
+      const char * lnl0 = gs_trace_lnl(s, &stride);
+      if (!sampler_step(s, 4) || !rowlog_emit(s, lnl0, stride, nullptr)) return 0;
+    }
   }
   return gs_join(s);                 // whoever uses the engine's stream next sees both halves
 }
@@ -1313,15 +1316,11 @@ static int gs_level_roots(bpa_sampler * s)
   return ok;
 }
 
-// settle whatever is pending and bring the trees to the host
-static int gs_download(bpa_sampler * s)
+// the end of a download, either sampler's, behind the copy of its trees: the substitution parameters, the rates with their
+// mean and the heredity scalars, where the sampler has them — and the wait for all of it
+static int gs_download_tail(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
-  if (!gs_step(s, 4) || !gs_level_roots(s) || !gs_prog_pull(s)) return 0;
-  // the settle launch rolls rejected frequency / exchangeability proposals back in the parameter blocks: the loci's
-  // eigensystems must follow before anyone else (bpa_batch_evaluate, a plan) computes P-matrices from them
-  if (!gs_refresh_eigen(s)) return 0;
-  HIPCHK(hipMemcpyAsync(s->g_trees.data(), s->g_dev.p, s->nloci*sizeof(gsm::GTree), hipMemcpyDeviceToHost, e->stream));
   if (s->g_sm.p && !s->g_sm_host.empty())
     HIPCHK(hipMemcpyAsync(s->g_sm_host.data(), s->g_sm.p, s->g_sm_host.size()*sizeof(double), hipMemcpyDeviceToHost, e->stream));
   if (s->g_mui.p)
@@ -1332,6 +1331,18 @@ static int gs_download(bpa_sampler * s)
   if (s->g_hered.p) HIPCHK(hipMemcpyAsync(s->g_hered_host.data(), s->g_hered.p, s->nloci*sizeof(double), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return 1;
+}
+
+// settle whatever is pending and bring the trees to the host
+static int gs_download(bpa_sampler * s)
+{
+  bpa_engine * e = s->eng;
+  if (!gs_step(s, 4) || !gs_level_roots(s) || !gs_prog_pull(s)) return 0;
+  // the settle launch rolls rejected frequency / exchangeability proposals back in the parameter blocks: the loci's
+  // eigensystems must follow before anyone else (bpa_batch_evaluate, a plan) computes P-matrices from them
+  if (!gs_refresh_eigen(s)) return 0;
+  HIPCHK(hipMemcpyAsync(s->g_trees.data(), s->g_dev.p, s->nloci*sizeof(gsm::GTree), hipMemcpyDeviceToHost, e->stream));
+  return gs_download_tail(s);
 }
 
 // ---- substitution-parameter moves: the sampler's copy of every locus's values and the window widths

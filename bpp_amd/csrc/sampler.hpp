@@ -1573,9 +1573,13 @@ static int gs_initialize(bpa_sampler * s);
 static int gs_iterate(bpa_sampler * s, unsigned iterations);
 static int gs_download(bpa_sampler * s);
 static int gb_upload(bpa_sampler * s);
+static int gb_subst_ready(bpa_sampler * s);
 static int gb_initialize(bpa_sampler * s);
-static int gb_iterate(bpa_sampler * s, unsigned iterations);
 static int gb_download(bpa_sampler * s);
+// one step launch / one evaluation of the sampler's own kind, gs_step / gs_eval or gb_step / gb_eval (bigsampler_host.hpp, below
+// both pairs): the generic and the big-tree sampler run ONE launch loop of an iteration (gs_iterate) through these two
+static inline int sampler_step(bpa_sampler * s, unsigned mode, unsigned k = 0, double tau_u = 0, double mix_c = 1.0, double mix_lnc = 0);
+static inline int sampler_eval(bpa_sampler * s, int kind);
 
 // ---- the persistent iteration kernel (sweep2.hpp): tables, eligibility, launch
 template <int NT> static size_t v2_lds_base(bool prog)
@@ -2583,6 +2587,37 @@ extern "C" int bpa_sampler_set_p2p(bpa_sampler_t * s, bpa_p2p_t * p, unsigned fi
   return 1;
 }
 
+// THETA with uniform windows for every population that can hold a coalescence, from the statistics the step before left (the
+// caller settles it first): the sums and the (independent) decisions in one launch; the next launch (any mode) takes every
+// tree's density again with the new thetas.  hered: the loci's heredity scalars, null where the sampler has none
+static int theta_uniform_step(bpa_sampler * s, const double * hered)
+{
+  bpa_engine * e = s->eng;
+  smp::ThetaArgs ta{};
+  for (int p = 0; p < s->sp.npop; ++p)
+    if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
+  if (!s->allreduce)
+    hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
+                       s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, hered);
+  else
+  {
+    hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
+                       s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0, hered);
+    // all populations' sums in ONE collective, in the memory the callback's collective addresses
+    double * ar = s->sum_ext ? s->sum_ext : s->theta_sums.p;
+    const size_t nb = (size_t)s->sp.npop*sizeof(double);
+    if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(ar, s->theta_sums.p, nb, hipMemcpyDeviceToDevice, e->stream));
+    if (!s->allreduce(s->allreduce_ctx, ar, (unsigned)s->sp.npop, (void *)e->stream)) return fail("bpa_sampler: the all-reduce callback failed");
+    if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(s->theta_sums.p, ar, nb, hipMemcpyDeviceToDevice, e->stream));
+    hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
+                       s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1, hered);
+  }
+  HIPCHK(hipGetLastError());
+  s->logpr_stale = true;
+  s->launches += 1;
+  return 1;
+}
+
 extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
 {
   bpa_engine * e = s->eng;
@@ -2596,8 +2631,7 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
     return fail("bpa_sampler_iterate: the heredity move runs on one rank (an all-reduce callback or the mailboxes are installed)");
   if (!sampler_upload(s)) return 0;
   s->host_current = false;
-  if (s->big) return gb_iterate(s, iterations);
-  if (s->generic) return gs_iterate(s, iterations);
+  if (s->generic || s->big) return gs_iterate(s, iterations);
   if (s->v2_ok && !s->allreduce && !s->opt.launch_times) return sampler_iterate_v2(s, iterations, true);
   if (s->kernel_bpp) return fail("bpa_sampler: BPP's proposal kernel runs in the persistent iteration kernel only (one GPU, or several with bpa_sampler_set_p2p)");
   // several ranks: the per-locus sweep by the persistent kernel (one launch), the all-loci steps one launch each
@@ -2610,33 +2644,7 @@ extern "C" int bpa_sampler_iterate(bpa_sampler_t * s, unsigned iterations)
       if (!sampler_launch(s, 0, 1.0)) return 0;                  // GAGE + GSPR of every locus (settles a pending mix first)
       s->sweeps++;
     }
-    if (s->sp.theta_alpha > 0)
-    {
-      // THETA for every population that can hold a coalescence, from the statistics the sweep just stored: the sums and
-      // the (independent) decisions in one launch, then every locus's density with the new thetas
-      smp::ThetaArgs ta{};
-      for (int p = 0; p < s->sp.npop; ++p)
-        if (s->has_theta[p]) { ta.on[p] = 1u; ta.win_u[p] = a00_rndu(&s->grng); ta.uacc[p] = a00_rndu(&s->grng); }
-      if (!s->allreduce)
-        hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)nullptr, 1, (const double *)nullptr);
-      else
-      {
-        hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, s->theta_sums.p, (const double *)nullptr, 0, (const double *)nullptr);
-        // all populations' sums in ONE collective, in the memory the callback's collective addresses
-        double * ar = s->sum_ext ? s->sum_ext : s->theta_sums.p;
-        const size_t nb = (size_t)s->sp.npop*sizeof(double);
-        if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(ar, s->theta_sums.p, nb, hipMemcpyDeviceToDevice, e->stream));
-        if (!s->allreduce(s->allreduce_ctx, ar, (unsigned)s->sp.npop, (void *)e->stream)) return fail("bpa_sampler: the all-reduce callback failed");
-        if (ar != s->theta_sums.p) HIPCHK(hipMemcpyAsync(s->theta_sums.p, ar, nb, hipMemcpyDeviceToDevice, e->stream));
-        hipLaunchKernelGGL(smp::theta_sum_decide_kernel, dim3(s->sp.npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p,
-                           s->nloci, s->taus.p, s->sp, ta, s->counters.p, (double *)nullptr, (const double *)s->theta_sums.p, 1, (const double *)nullptr);
-      }
-      s->logpr_stale = true;        // the next launch (any mode) recomputes every tree's density with the new thetas
-      HIPCHK(hipGetLastError());
-      s->launches += 1;
-    }
+    if (s->sp.theta_alpha > 0 && !theta_uniform_step(s, nullptr)) return 0;        // (the sweep just stored the statistics)
     for (int q = s->sp.S; q < s->sp.npop; ++q)                    // one rubber-band step per species divergence
     {
       const double uprop = a00_rndu(&s->grng), uacc_t = a00_rndu(&s->grng);

@@ -1,6 +1,6 @@
 """Per-locus mutation rates and heredity scalars on the big-tree device sampler (csrc/bigsampler.hpp: the h of tree_logpr, the
 lengths x mu_i of the record loop, step modes 9 — MUI, settled as pend 4 — and 10 — HRDT — of big_step_kernel, both
-instantiations; csrc/bigsampler_host.hpp: gb_scalars / gb_mubar) against the C host driver on the same library, against the
+instantiations; csrc/gsampler_host.hpp: gs_iterate's tail / gs_mubar) against the C host driver on the same library, against the
 oracle's scale counters at lengths x mu_i, against a CPU recompute, against the priors, and what stays refused.
 CPU twin: tests/test_bigsampler_scalars_host.py; the generic sampler's tests: tests/test_gpu_heredity.py, tests/test_gpu_locusrates.py."""
 import json

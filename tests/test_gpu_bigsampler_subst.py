@@ -1,6 +1,6 @@
 """The substitution-parameter moves on the big-tree device sampler (csrc/bigsampler.hpp: step modes 6 — base frequency k —,
 7 — exchangeability k — and 8 — alpha — of big_step_kernel, both instantiations, settled as pend 4; big_par_kernel, which
-brings a locus's parameter block and eigensystem level with the sampler's copy; csrc/bigsampler_host.hpp: gb_scalars) against
+brings a locus's parameter block and eigensystem level with the sampler's copy; csrc/gsampler_host.hpp: gs_iterate's tail) against
 the C host driver on the same library, against the oracle's scale counters at the current parameters, against a CPU
 recompute, against the prior, and what is refused.
 CPU twin: tests/test_bigsampler_subst_host.py; the generic sampler's tests: tests/test_gpu_gsampler.py, tests/test_gpu_subst_edges.py."""

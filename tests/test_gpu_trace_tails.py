@@ -2,7 +2,7 @@
 
  A. under the moves that follow MIX in an iteration — HRDT, the nine substitution-parameter steps, MUI (left pending when the
     rates' mean is fixed), MUBAR — on the generic and on the big-tree sampler, and under the inverse-gamma priors; the row is
-    written behind the settle of whichever step closed the iteration (gs_iterate / gb_iterate: the extra step of mode 4);
+    written behind the settle of whichever step closed the iteration (gs_iterate, either sampler's: the extra step of mode 4);
  B. on more loci than trace_row_kernel has threads (1 025 and 2 500: the second and third trip of its loop);
  C. the buffer hand-over, partial reads, the burn-in's hold and a second set_trace off the persistent kernel: on the generic
     sampler (part-batches on several streams), the big-tree sampler and a composite (the merge of the parts' rows).
