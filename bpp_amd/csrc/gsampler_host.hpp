@@ -751,9 +751,10 @@ static int gs_initialize(bpa_sampler * s)
 }
 
 // ======================= the program's THETA / TAU / MIX on a generic sampler: decisions on the host =======================
-// theta_step_gibbs / tau_step / mix_step of csrc/host/a00_driver.c, statement for statement on the host side (same global
-// stream, same order of draws: [first TAU's window] [THETA: choices + windows] [Gibbs variates] [acceptance numbers] [TAU:
-// variates, acceptance] [next window] ...), the loci's part — proposal, likelihood, the sums — on the device.
+// The decisions are include/bpp_amd_priors.h's a00_prog_*, which theta_step_gibbs / tau_step / mix_step of csrc/host/a00_driver.c
+// call too: ONE statement, one order of draws ([first TAU's window] [THETA: choices + windows] [Gibbs variates] [acceptance
+// numbers] [TAU: variates, acceptance] [next window] ...).  Here is the sampler's own: the loci's part on the device, fetching the
+// sums (gs_prog_out / _fetch), their way through an all-reduce (gs_split64 / gs_join64), GApply, gp_pj and the [gsp] log line.
 static void gs_declog(const bpa_sampler * s, const char * what, int k, double lnacc, int acc)
 {
   if (s->opt.decision_log) fprintf(stderr, "[gsp] %s %d lnacc %.17g u -1 -> %d\n", what, k, lnacc, acc);
@@ -886,26 +887,30 @@ static int gs_prog_apply(bpa_sampler * s, const gsm::GApply & a, bool with_flag)
   return 1;
 }
 
+static uint32_t gs_theta_mask(const bpa_sampler * s)
+{
+  uint32_t m = 0;
+  for (int p = 0; p < s->sp.npop; ++p) if (s->has_theta[p]) m |= 1u << p;
+  return m;
+}
+// the sampler's arrays for the program's decisions (a00_prog_*); gz: the caller's copy of the global stream's state
+static a00_prog_t gs_prog_view(bpa_sampler * s, unsigned int * gz)
+{
+  return a00_prog_t{s->sp.npop, gs_theta_mask(s), smp::theta_kind(s->sp), s->sp.theta_alpha, s->sp.theta_beta, s->gp_k, s->gp_T, s->gp_ok, s->gp_theta, gz};
+}
+
 static int gs_prog_theta(bpa_sampler * s)
 {
   bpa_engine * e = s->eng;
   const int npop = s->sp.npop;
   unsigned int gz = (unsigned int)s->grng;
-  int slide[smp::MAXPOP]; double tnew[smp::MAXPOP], fa[smp::MAXPOP], fb[smp::MAXPOP];
-  const int tk = smp::theta_kind(s->sp);
-  uint32_t onmask = 0;
-  for (int p = 0; p < npop; ++p)
-  {
-    slide[p] = 0; tnew[p] = s->gp_theta[p];
-    if (!s->has_theta[p]) continue;
-    onmask |= 1u << p;
-    slide[p] = a00_bpp_rndu(&gz) < s->sp.theta_slide_prob;
-    if (slide[p]) tnew[p] = a00_reflect(s->gp_theta[p] + s->sp.ft_theta*a00_bpp_rnd_symmetrical(&gz), 0.0, 999.0);
-  }
+  int slide[smp::MAXPOP], acc[smp::MAXPOP]; double tnew[smp::MAXPOP], lnacc[smp::MAXPOP];
+  a00_prog_t g = gs_prog_view(s, &gz);
+  a00_prog_theta_propose(&g, s->sp.theta_slide_prob, s->sp.ft_theta, slide, tnew);
   long long h[3*smp::MAXPOP];
   unsigned long long pseq = 0;
   double * pout = gs_prog_out(s, &pseq);
-  hipLaunchKernelGGL(gsm::gprog_theta_sums_kernel, dim3(npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p, s->nloci, onmask,
+  hipLaunchKernelGGL(gsm::gprog_theta_sums_kernel, dim3(npop), dim3(1024), 0, e->stream, s->pop_nc.p, s->pop_t2h.p, s->nloci, (uint32_t)g.has,
                      reinterpret_cast<long long *>(pout), pseq, (const double *)s->g_hered.p);
   HIPCHK(hipGetLastError());
   if (!gs_prog_fetch(s, pout, h, (size_t)3*npop*sizeof(long long), pseq, npop)) return 0;
@@ -922,35 +927,18 @@ static int gs_prog_theta(bpa_sampler * s)
   }
   s->launches++;
   bool bad = false;
-  for (int p = 0; p < npop; ++p) { bad = bad || h[3*p + 2] != 0; s->gp_k[p] = h[3*p]; s->gp_T[p] = (double)h[3*p + 1]*(1.0/1099511627776.0); }
-  s->gp_ok = !bad;
-  for (int p = 0; p < npop; ++p)
-  {
-    fa[p] = fb[p] = NAN;
-    if (!s->has_theta[p] || bad || slide[p]) continue;
-    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, (long)s->gp_k[p], s->gp_T[p], &fa[p], &fb[p]);
-    if (fa[p] == fa[p]) tnew[p] = 1/(a00_bpp_rndgamma(&gz, fa[p])/fb[p]);
-  }
+  for (int p = 0; p < npop; ++p) { bad = bad || h[3*p + 2] != 0; s->gp_k[p] = h[3*p]; s->gp_T[p] = (double)h[3*p + 1]*A00_FX40_INV; }
+  g.ok = s->gp_ok = !bad;
+  a00_prog_theta_decide(&g, slide, tnew, acc, lnacc);
   gsm::GApply a{};
   a.accept = 1u; a.set_tau_q = 0xffffffffu;
   for (int p = 0; p < npop; ++p)
   {
-    double lnacc = NAN; bool acc = false;
     if (!s->has_theta[p]) continue;
     a.nprop++;
-    const double T = s->gp_T[p];
-    if (!bad)
-    {
-      if (slide[p]) lnacc = a00_theta_lnacc_kind(tk, (long)s->gp_k[p], T, s->gp_theta[p], tnew[p], s->sp.theta_alpha, s->sp.theta_beta);
-      else if (fa[p] == fa[p] && tk == A00_PRIOR_INVGAMMA) lnacc = tnew[p] == tnew[p] ? 0.0 : NAN;      // (the conditional itself: accepted, nothing drawn)
-      else if (fa[p] == fa[p])
-        lnacc = a00_theta_lnacc((long)s->gp_k[p], T, s->gp_theta[p], tnew[p], s->sp.theta_alpha, s->sp.theta_beta)
-              + a00_theta_gibbs_hastings(fa[p], fb[p], s->gp_theta[p], tnew[p]);
-      acc = lnacc == lnacc && tnew[p] > 0 && (lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc));
-    }
-    gs_declog(s, slide[p] ? "theta" : "thetag", p, lnacc, acc);
-    if (slide[p]) { s->gp_pj[8]++; s->gp_pj[9] += acc ? 1u : 0u; }
-    if (acc) { a.nacc++; s->gp_theta[p] = tnew[p]; a.theta_mask |= 1u << p; a.theta[p] = tnew[p]; if (!slide[p]) a.ngacc++; }
+    gs_declog(s, slide[p] ? "theta" : "thetag", p, lnacc[p], acc[p]);
+    if (slide[p]) { s->gp_pj[8]++; s->gp_pj[9] += acc[p] ? 1u : 0u; }
+    if (acc[p]) { a.nacc++; a.theta_mask |= 1u << p; a.theta[p] = tnew[p]; if (!slide[p]) a.ngacc++; }
     if (!slide[p]) a.ngprop++;
   }
   s->grng = (a00_rng_t)gz;
@@ -994,29 +982,12 @@ static int gs_prog_tau(bpa_sampler * s, int q)
   const long long * ol = reinterpret_cast<const long long *>(out);
   const bool bad = ol[4] != 0;
   if (pq < 0 && s->sp.tau_alpha > 0) sum += a00_tau_prior_lnratio(smp::tau_kind(s->sp), s->sp.tau_alpha, s->sp.tau_beta, s->sp.S, old, tnew);
-  const int tk = smp::theta_kind(s->sp);
   gsm::GApply a{};
   a.set_tau_q = (uint32_t)q; a.tau_new = tnew; a.nprop = 1;
-  double oldtheta[3], Cn[3] = {0, 0, 0};
-  for (int j = 0; j < 3; ++j)
-  {
-    const int p = aff[j]; const double to = s->gp_theta[p]; const long k = (long)s->gp_k[p];
-    oldtheta[j] = to;
-    if (!s->has_theta[p]) continue;
-    if (bad || !s->gp_ok) { sum = NAN; continue; }
-    double a1, b1, a1o, b1o;
-    Cn[j] = (double)ol[1 + j]*(1.0/1099511627776.0);
-    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, Cn[j], &a1, &b1);
-    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, s->gp_T[p], &a1o, &b1o);
-    if (!(a1 == a1 && a1o == a1o)) { sum = NAN; continue; }
-    const double g = a00_bpp_rndgamma(&gz, a1);
-    const double tn = 1.0/(g/b1);
-    sum += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-         + a00_theta_prior_lnratio(tk, s->sp.theta_alpha, s->sp.theta_beta, to, tn)
-         + (k*(std::log(2.0/tn) - std::log(2.0/to)) - (Cn[j]/tn - s->gp_T[p]/to));
-    s->gp_theta[p] = tn;
-  }
-  const bool acc = sum >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(sum);
+  double oldtheta[3], Cn[3];
+  const a00_prog_t g = gs_prog_view(s, &gz);
+  sum = a00_prog_tau_lnacc(&g, aff, ol + 1, !bad, sum, Cn, oldtheta);
+  const bool acc = a00_bpp_accept(&gz, sum);
   gs_declog(s, "tau", q, sum, acc);
   s->gp_pj[4]++; s->gp_pj[5] += acc ? 1u : 0u;
   s->grng = (a00_rng_t)gz;
@@ -1037,26 +1008,9 @@ static int gs_prog_mix(bpa_sampler * s)
   unsigned int gz = (unsigned int)s->grng;
   const int npop = s->sp.npop;
   const double lnc = s->sp.ft_mix*a00_bpp_rnd_symmetrical(&gz), c = std::exp(lnc);
-  double oldtheta[smp::MAXPOP], lnacc_theta = 0;
-  const int tk = smp::theta_kind(s->sp);
-  for (int p = 0; p < npop; ++p) oldtheta[p] = s->gp_theta[p];
-  for (int p = 0; p < npop; ++p)
-  {
-    const double to = oldtheta[p]; const long k = (long)s->gp_k[p];
-    if (!s->has_theta[p]) continue;
-    if (!s->gp_ok) { lnacc_theta = NAN; continue; }
-    double a1, b1, a1o, b1o;
-    const double Ts = s->gp_T[p]*c;
-    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, Ts, &a1, &b1);
-    a00_theta_conditional_kind(tk, s->sp.theta_alpha, s->sp.theta_beta, k, Ts/c, &a1o, &b1o);
-    if (!(a1 == a1 && a1o == a1o)) { lnacc_theta = NAN; continue; }
-    const double g = a00_bpp_rndgamma(&gz, a1);
-    const double tn = 1.0/(g/b1);
-    lnacc_theta += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-                 + a00_theta_prior_lnratio(tk, s->sp.theta_alpha, s->sp.theta_beta, to, tn)
-                 + (k*(std::log(2.0/tn) - std::log(2.0/to)) - (Ts/tn - s->gp_T[p]/to));
-    s->gp_theta[p] = tn;
-  }
+  double oldtheta[smp::MAXPOP];
+  const a00_prog_t g = gs_prog_view(s, &gz);
+  const double lnacc_theta = a00_prog_mix_thetas(&g, c, oldtheta);
   s->grng = (a00_rng_t)gz;
   if (!gs_step(s, 3, 0, 0.0, c, lnc) || !gs_eval(s, 1)) return 0;
   double out[8];
@@ -1069,11 +1023,8 @@ static int gs_prog_mix(bpa_sampler * s)
   s->launches++;
   if (s->allreduce && !gs_prog_allreduce(s, out, 1u)) return 0;
   const int root = npop - 1;
-  double lnacc = out[0] + (double)(s->sp.S - 1)*lnc;
-  if (s->sp.tau_alpha > 0)
-    lnacc += a00_mix_tau_prior_lnratio(smp::tau_kind(s->sp), s->sp.tau_alpha, s->sp.tau_beta, s->sp.S, lnc, s->gp_tau[root], s->gp_tau[root]*c);
-  lnacc += lnacc_theta;
-  const bool acc = lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc);
+  const double lnacc = a00_mix_lnacc(out[0], s->sp.S, lnc, smp::tau_kind(s->sp), s->sp.tau_alpha, s->sp.tau_beta, s->gp_tau[root], s->gp_tau[root]*c, lnacc_theta);
+  const bool acc = a00_bpp_accept(&gz, lnacc);
   gs_declog(s, "mix", 0, lnacc, acc);
   s->gp_pj[6]++; s->gp_pj[7] += acc ? 1u : 0u;
   s->grng = (a00_rng_t)gz;
@@ -1090,12 +1041,6 @@ static int gs_prog_mix(bpa_sampler * s)
 }
 
 // ---- the same three steps with the decision on the device: sums -> [the ranks' collective] -> gdec_kernel, no synchronisation
-static uint32_t gs_theta_mask(const bpa_sampler * s)
-{
-  uint32_t m = 0;
-  for (int p = 0; p < s->sp.npop; ++p) if (s->has_theta[p]) m |= 1u << p;
-  return m;
-}
 // n doubles of g_dsum summed over the ranks, BPA_SAMPLER_SUMS at a time, in the callback's buffer (the caller's device_sums or
 // the sampler's own): copy in, collective, copy back — all enqueued on the engine's stream
 static int gs_dev_allreduce(bpa_sampler * s, unsigned n)
@@ -1182,7 +1127,7 @@ static int gs_mubar(bpa_sampler * s)
     const double l_old = std::log(st.mubar), l_new = a00_reflect(l_old + ft*a00_bpp_rnd_symmetrical(&gz), -99.0, 99.0);
     const double m_new = std::exp(l_new);
     const double lnacc = A00_MUBAR_LNACC(l_old, l_new, st.mubar, m_new, am/st.mubar, am/m_new, am, a, b, (double)s->nloci, st.sum);
-    const bool acc = lnacc >= -1e-10 || a00_bpp_rndu(&gz) < std::exp(lnacc);
+    const bool acc = a00_bpp_accept(&gz, lnacc);
     gs_declog(s, "mubar", 0, lnacc, acc);
     s->grng = (a00_rng_t)gz;
     hipLaunchKernelGGL((gsm::gmubar_kernel<3>), dim3(1), dim3(1), 0, e->stream, (const double *)s->g_mui.p, s->nloci, s->g_lr.p, (uint32_t *)nullptr, ft, am, a, b, acc ? m_new : 0.0, 0.0);

@@ -123,7 +123,7 @@ static void skip_u(a00_driver_t * d, long i) { if (d->kernel != A00_KERNEL_BPP) 
 /* Metropolis-Hastings acceptance; u0: a uniform drawn in advance (uniform kernel, all-loci steps), < 0 = draw now */
 static int accept(a00_driver_t * d, long i, double lnacc, double u0)
 {
-  if (d->kernel == A00_KERNEL_BPP) return lnacc >= -1e-10 || a00_bpp_rndu(i < 0 ? &d->gz : d->zrng + i) < exp(lnacc);
+  if (d->kernel == A00_KERNEL_BPP) return a00_bpp_accept(i < 0 ? &d->gz : d->zrng + i, lnacc);
   if (u0 < 0) u0 = draw_u(d, i);
   return lnacc >= 0 || u0 < exp(lnacc);
 }
@@ -890,7 +890,7 @@ static int theta_sums(a00_driver_t * d, long long * ksum, long long * tsum)
         {
           const double x = d->hered ? t2h[pp]/d->hered[li] : t2h[pp];
           if (!(fabs(x) < 256.0)) badl = 1;
-          else { kl[pp] += nc[pp]; tl[pp] += llrint(x*1099511627776.0); }
+          else { kl[pp] += nc[pp]; tl[pp] += llrint(x*A00_FX40); }
         }
     }
 #pragma omp critical
@@ -899,52 +899,32 @@ static int theta_sums(a00_driver_t * d, long long * ksum, long long * tsum)
   return !bad;
 }
 
-/* THETA the program's way (a00_set_program_moves, A00_KERNEL_BPP): per theta, in population order, the sliding
-   window with probability slide_prob, else the metropolized Gibbs draw of bpp_amd_host.h — both decided from
-   k_p = sum over loci of the coalescences in p and T_p = sum of T2h (2^-40 fixed point: no order).  Global stream:
-   the choices (and the windows of the sliding ones) of all populations first, then per population the Gibbs variate
-   and the acceptance number (drawn only when needed) — the order the device kernel can follow with ONE exchange.   */
+/* the driver's arrays for the program's decisions (bpp_amd_priors.h: a00_prog_*) */
+static a00_prog_t prog_view(a00_driver_t * d)
+{
+  a00_prog_t g = { d->npop, 0, d->theta_kind, d->theta_alpha, d->theta_beta, d->run_k, d->run_T, d->run_ok, d->theta, &d->gz }; int p;
+  for (p = 0; p < d->npop; ++p) if (d->has_theta[p]) g.has |= 1u << p;
+  return g;
+}
+
+/* THETA the program's way (a00_set_program_moves, A00_KERNEL_BPP): per theta, in population order, the sliding window with
+   probability slide_prob, else the metropolized Gibbs draw — both decided from k_p = sum over loci of the coalescences in p
+   and T_p = sum of T2h (2^-40 fixed point: no order).  The decisions and the order of their draws: a00_prog_theta_*.  */
 static int theta_step_gibbs(a00_driver_t * d)
 {
-  int p, slide[A00_MAXPOP], bad = 0; long li;
-  double tnew[A00_MAXPOP], fa[A00_MAXPOP], fb[A00_MAXPOP];
-  long long ksum[A00_MAXPOP], tsum[A00_MAXPOP];
+  int p, slide[A00_MAXPOP], acc_[A00_MAXPOP]; long li;
+  double tnew[A00_MAXPOP], lnacc[A00_MAXPOP]; long long tsum[A00_MAXPOP];
+  a00_prog_t g = prog_view(d);
+  a00_prog_theta_propose(&g, d->theta_slide_prob, d->ft_theta, slide, tnew);
+  g.ok = d->run_ok = theta_sums(d, d->run_k, tsum);
+  for (p = 0; p < d->npop; ++p) d->run_T[p] = (double)tsum[p]*A00_FX40_INV;
+  a00_prog_theta_decide(&g, slide, tnew, acc_, lnacc);
   for (p = 0; p < d->npop; ++p)
   {
-    slide[p] = 0; tnew[p] = d->theta[p];
-    if (!d->has_theta[p]) continue;
-    slide[p] = a00_bpp_rndu(&d->gz) < d->theta_slide_prob;
-    if (slide[p]) tnew[p] = a00_reflect(d->theta[p] + d->ft_theta*draw_window(d, -1), 0.0, 999.0);
-  }
-  bad = !theta_sums(d, ksum, tsum);
-  d->run_ok = !bad;
-  for (p = 0; p < d->npop; ++p) { d->run_k[p] = ksum[p]; d->run_T[p] = (double)tsum[p]*(1.0/1099511627776.0); }
-  /* the Gibbs variates of all populations first (the device takes them side by side), then the decisions */
-  for (p = 0; p < d->npop; ++p)
-  {
-    fa[p] = fb[p] = NAN;
-    if (!d->has_theta[p] || bad || slide[p]) continue;
-    a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, (long)ksum[p], d->run_T[p], &fa[p], &fb[p]);
-    if (fa[p] == fa[p]) tnew[p] = 1/(a00_bpp_rndgamma(&d->gz, fa[p])/fb[p]);
-  }
-  for (p = 0; p < d->npop; ++p)
-  {
-    double lnacc = NAN, T; int acc_ = 0;
     if (!d->has_theta[p]) continue;
     d->proposals++;
-    T = d->run_T[p];
-    if (!bad)
-    {
-      if (slide[p]) lnacc = a00_theta_lnacc_kind(d->theta_kind, (long)ksum[p], T, d->theta[p], tnew[p], d->theta_alpha, d->theta_beta);
-      else if (fa[p] == fa[p] && d->theta_kind == A00_PRIOR_INVGAMMA)
-        lnacc = tnew[p] == tnew[p] ? 0.0 : NAN;          /* a draw from the conditional itself: accepted, no acceptance number (stree.c:3822) */
-      else if (fa[p] == fa[p])
-        lnacc = a00_theta_lnacc((long)ksum[p], T, d->theta[p], tnew[p], d->theta_alpha, d->theta_beta)
-              + a00_theta_gibbs_hastings(fa[p], fb[p], d->theta[p], tnew[p]);
-      acc_ = lnacc == lnacc && tnew[p] > 0 && accept(d, -1, lnacc, -1.0);
-    }
-    declog(slide[p] ? "theta" : "thetag", p, lnacc, -1.0, acc_);
-    if (acc_) { d->accepted++; d->theta[p] = tnew[p]; if (!slide[p]) d->gibbs_accepted++; }
+    declog(slide[p] ? "theta" : "thetag", p, lnacc[p], -1.0, acc_[p]);
+    if (acc_[p]) { d->accepted++; if (!slide[p]) d->gibbs_accepted++; }
     if (!slide[p]) d->gibbs_proposals++;
   }
 #pragma omp parallel for schedule(static) num_threads(d->threads) if (d->threads > 1)
@@ -962,13 +942,12 @@ static int tau_step(a00_driver_t * d, int q)
   const int nco = d->ncohort == 2 ? 2 : 1;
   const int cl = d->sp_left[q], cr = d->sp_right[q], pq = d->sp_parent[q];
   /* the program's rubber band also re-draws the thetas of q and its two children (opt_rb_theta_update = 1, bpp.c:618;
-     propose_tau, stree.c:5840-5990): each from the inverse-gamma fitted to its conditional given k_p and the sum of the
-     T2h AFTER the move; the densities' change over all loci then follows from the sums, the loci contribute their
-     likelihood change and their three new T2h */
+     propose_tau, stree.c:5840-5990; a00_prog_tau_lnacc): the loci contribute their likelihood change and their three new T2h */
   const int program = d->kernel == A00_KERNEL_BPP && d->program_moves && d->theta_alpha > 0;
   const int aff[3] = { q, cl, cr };
   long long cnew[3] = { 0, 0, 0 };
-  double oldtheta[3];
+  double oldtheta[3], Cn[3] = { 0, 0, 0 };
+  a00_prog_t g = prog_view(d);
   const double old = d->tau[q], lo = fmax(d->tau[cl], d->tau[cr]), hi = pq >= 0 ? d->tau[pq] : 999.0;
   const double tnew = a00_reflect(old + d->ft_tau*(d->pre_valid ? d->pre_window : draw_window(d, -1)), lo, hi);
   const double uacc = d->kernel == A00_KERNEL_BPP ? -1.0 : draw_u(d, -1);
@@ -1027,25 +1006,9 @@ static int tau_step(a00_driver_t * d, int q)
       for (j = 0; j < 3; ++j)
       {
         const double x = d->w_diff[(size_t)i*A00_MAXPOP + j];
-        if (!(fabs(x) < 256.0)) bad = 1; else cnew[j] += llrint(x*1099511627776.0);
+        if (!(fabs(x) < 256.0)) bad = 1; else cnew[j] += llrint(x*A00_FX40);
       }
-    for (j = 0; j < 3; ++j)
-    {
-      const int p = aff[j]; double a1, b1, a1o, b1o, g, tn, Cn; const double to = d->theta[p]; const long k = (long)d->run_k[p];
-      oldtheta[j] = to;
-      if (!d->has_theta[p]) continue;
-      if (bad || !d->run_ok) { sum = NAN; continue; }
-      Cn = (double)cnew[j]*(1.0/1099511627776.0);
-      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, Cn, &a1, &b1);
-      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, d->run_T[p], &a1o, &b1o);
-      if (!(a1 == a1 && a1o == a1o)) { sum = NAN; continue; }
-      g = a00_bpp_rndgamma(&d->gz, a1);
-      tn = 1.0/(g/b1);
-      sum += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-           + a00_theta_prior_lnratio(d->theta_kind, d->theta_alpha, d->theta_beta, to, tn)
-           + (k*(log(2.0/tn) - log(2.0/to)) - (Cn/tn - d->run_T[p]/to));
-      d->theta[p] = tn;
-    }
+    sum = a00_prog_tau_lnacc(&g, aff, cnew, !bad, sum, Cn, oldtheta);
   }
   d->proposals++;
   acc_ = accept(d, -1, sum, uacc);
@@ -1055,7 +1018,7 @@ static int tau_step(a00_driver_t * d, int q)
     d->accepted++;
     if (program)
     {
-      for (j = 0; j < 3; ++j) if (d->has_theta[aff[j]]) d->run_T[aff[j]] = (double)cnew[j]*(1.0/1099511627776.0);
+      for (j = 0; j < 3; ++j) if (d->has_theta[aff[j]]) d->run_T[aff[j]] = Cn[j];
 #pragma omp parallel for schedule(static) num_threads(d->threads) if (d->threads > 1)
       for (li = 0; li < (long)d->nloci; ++li) d->p_logpr[li] = tree_logpr(d, d->trees + li);        /* (with the new thetas) */
     }
@@ -1084,27 +1047,7 @@ static int mix_step(a00_driver_t * d)
   const int program = d->kernel == A00_KERNEL_BPP && d->program_moves && d->theta_alpha > 0;
   if (!staging_ready(d)) return 0;
   for (p = 0; p < d->npop; ++p) oldtheta[p] = d->theta[p];
-  if (program)
-  {
-    /* the thetas from their conditionals given the scaled trees (prop_mixing.c:272-425), in population order; the
-       densities' change over all loci follows from the sums: k (log 2/theta' - log 2/theta) - (c T/theta' - T/theta) */
-    for (p = 0; p < d->npop; ++p)
-    {
-      double a1, b1, a1o, b1o, Ts, g, tn; const double to = oldtheta[p]; const long k = (long)d->run_k[p];
-      if (!d->has_theta[p]) continue;
-      if (!d->run_ok) { lnacc_theta = NAN; continue; }
-      Ts = d->run_T[p]*c;
-      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, Ts, &a1, &b1);
-      a00_theta_conditional_kind(d->theta_kind, d->theta_alpha, d->theta_beta, k, Ts/c, &a1o, &b1o);
-      if (!(a1 == a1 && a1o == a1o)) { lnacc_theta = NAN; continue; }
-      g = a00_bpp_rndgamma(&d->gz, a1);
-      tn = 1.0/(g/b1);
-      lnacc_theta += (a00_invgamma_logpdf(to, a1o, b1o) - a00_invgamma_logpdf(tn, a1, b1))
-                   + a00_theta_prior_lnratio(d->theta_kind, d->theta_alpha, d->theta_beta, to, tn)
-                   + (k*(log(2.0/tn) - log(2.0/to)) - (Ts/tn - d->run_T[p]/to));
-      d->theta[p] = tn;
-    }
-  }
+  if (program) { a00_prog_t g = prog_view(d); lnacc_theta = a00_prog_mix_thetas(&g, c, oldtheta); }     /* (the thetas, given the scaled trees) */
   for (p = 0; p < d->npop; ++p) { oldtau[p] = d->tau[p]; d->tau[p] *= c; }
   for (co = 0; co < nco; ++co)
   {
@@ -1130,10 +1073,7 @@ static int mix_step(a00_driver_t * d)
   if (nco == 2) { if (!cohort_collect(d)) return 0; }
   else if (!step_eval(d, d->nloci)) return 0;
   for (i = 0; i < d->nloci; ++i) sum += (d->b_lnl[i] - d->trees[i].lnl) + d->p_delta[i];
-  lnacc = sum + (double)(d->S - 1)*lnc;
-  if (d->tau_alpha > 0)                    /* all taus scale together: the Dirichlet part is unchanged */
-    lnacc += a00_mix_tau_prior_lnratio(d->tau_kind, d->tau_alpha, d->tau_beta, d->S, lnc, oldtau[d->npop-1], d->tau[d->npop-1]);
-  lnacc += lnacc_theta;
+  lnacc = a00_mix_lnacc(sum, d->S, lnc, d->tau_kind, d->tau_alpha, d->tau_beta, oldtau[d->npop-1], d->tau[d->npop-1], lnacc_theta);
   d->proposals++;
   acc_ = accept(d, -1, lnacc, uacc);
   declog("mix", 0, lnacc, uacc, acc_);

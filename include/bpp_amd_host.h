@@ -270,8 +270,23 @@ static inline A00_HD double a00_invgamma_logpdf(double x, double a, double b)
   return a*log(b) - lgamma(a) + (-a - 1)*log(x) - b/x;
 }
 
-/* the two prior families of the thetas and of the root tau (gamma / inverse gamma) and every expression that depends on
-   the family: A00_HD functions like the ones above, in a header of their own */
+/* reflection of x into (a,b) (reflect, gtree.c:3983) */
+static inline double a00_reflect(double x, double a, double b)
+{
+  const double w = b - a; double e; long n;
+  if (!(w > 0)) return a;
+  if (x >= a && x <= b) return x;
+  e = x < a ? a - x : x - b;
+  n = (long)(e/w);
+  e -= (double)n*w;
+  /* an even number of whole widths keeps the side the walk left from */
+  if ((x < a) == ((n & 1) == 0)) return a + e;
+  return b - e;
+}
+#define A00_MAXPOP 15                     /* populations of a species tree (a00_set_species_tree: up to 8 species) */
+
+/* the two prior families of the thetas and of the root tau (gamma / inverse gamma) and every expression that depends on the
+   family (A00_HD functions like the ones above) and, host only, the program's THETA / TAU / MIX decisions from the sums */
 #include "bpp_amd_priors.h"
 
 /* gene tree of one locus: tips 0..tips-1, inner nodes after; the root node object stays
@@ -312,9 +327,8 @@ int            a00_set_tree(a00_driver_t *, unsigned i, int tips, const int * le
 const a00_tree_t * a00_tree(const a00_driver_t *, unsigned i);
 /* The species tree: `species` tips (populations 0..species-1) and species-1 inner populations
    after them, children before parents (the root last); parent[] (-1 for the root), tau[] (0 for
-   tips) and theta[] have 2*species-1 entries, stree->nodes order (tips first).  species <= 8.
-   Must be set before a00_initialize.                                                             */
-#define A00_MAXPOP 15
+   tips) and theta[] have 2*species-1 entries, stree->nodes order (tips first).  species <= 8
+   (A00_MAXPOP populations).  Must be set before a00_initialize.                                  */
 int            a00_set_species_tree(a00_driver_t *, int species, const int * parent, const double * tau,
                                     const double * theta);
 /* species of the tips of locus i (default: tip k belongs to species k) */
@@ -378,19 +392,6 @@ unsigned       a00_get_taus(const a00_driver_t *, double * tau);
 /* MSC density of the current gene tree of locus i, recomputed from scratch */
 double         a00_locus_logpr(const a00_driver_t *, unsigned i);
 
-/* reflection of x into (a,b) (reflect, gtree.c:3983) */
-static inline double a00_reflect(double x, double a, double b)
-{
-  const double w = b - a; double e; long n;
-  if (!(w > 0)) return a;
-  if (x >= a && x <= b) return x;
-  e = x < a ? a - x : x - b;
-  n = (long)(e/w);
-  e -= (double)n*w;
-  /* an even number of whole widths keeps the side the walk left from */
-  if ((x < a) == ((n & 1) == 0)) return a + e;
-  return b - e;
-}
 /* gtree_update_logprob_contrib (gtree.c:3859-3955) for one population: tau = its start, ptau = its
    parent's tau (< 0 for the root), nin = lineages entering, times[ncoal] the coalescent times in it
    SORTED ascending; heredity multiplies theta as in the reference.  Same operations, same order. */

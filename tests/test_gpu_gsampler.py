@@ -263,8 +263,9 @@ def test_generic_sampler_with_the_program_s_moves_equals_host_driver(taxa, model
     per-locus proposals draw from the reference's generator with its Bactrian-Laplace windows and acceptance rule on the device
     (gsm2::gstep2_kernel<.., BPP>), THETA by the metropolized Gibbs draw, the thetas re-drawn inside the rubber band and the
     mixing step — decided ON THE DEVICE by one wave from the loci's sums (gsm::gdec_kernel: the persistent kernel's control-wave
-    functions; round 6) or, host_decisions=True, on the host (gs_prog_theta / _tau / _mix, the statements of theta_step_gibbs /
-    tau_step / mix_step of a00_driver.c).  Same trajectory as the C host driver with a00_set_program_moves on the same library."""
+    functions; round 6) or, host_decisions=True, on the host (gs_prog_theta / _tau / _mix: the a00_prog_* functions of
+    include/bpp_amd_priors.h, which theta_step_gibbs / tau_step / mix_step of a00_driver.c call too — one statement of the
+    decisions).  Same trajectory as the C host driver with a00_set_program_moves on the same library."""
     eng = bpp_amd.Engine(0)
     data = synth.make_dataset(nloci, 300, taxa, model, R, seed=41)
     loci_a = tape.make_engine_loci(eng, data)
